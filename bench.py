@@ -16,9 +16,11 @@ under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`
 128-byte RCCL id travels through a file handshake (ssdseglib/_parallel.py) -- no torch in this file or in the product path.  Weak scaling: each rank owns a
 32-image shard, one collective per step (gradients summed, BatchNorm moving statistics averaged).
 
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel symbol; durations from HIP events recorded around every launch of
-that kernel in the timed region, on the launch stream, inside the C library; bytes / flops per SURVEY.md 8(d)) and
-`cpu_baseline` (NumPy oracle of the same step, bounded sample).
+A plain run sets up, warms up, times `--steps` steps and has rank 0 print ONE JSON line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  `--full` adds what takes runs of its own: `roofline` (dominant kernel
+symbol; durations from HIP events recorded around every launch of that kernel in the timed region, on the launch stream,
+inside the C library; bytes / flops per SURVEY.md 8(d)) with the kernel survey step, `nms_boxes_per_sec`, and `cpu_baseline`
+(NumPy oracle of the same step, bounded sample).  `--dump-outputs DIR` writes what the last timed step computed as DIR/*.npy.
 """
 import argparse
 import ctypes as C
@@ -143,6 +145,17 @@ class BackboneStep:
             self.reducer()
         e.adam_step(lr=1e-4, grad_scale=self.reducer.scale if self.reducer is not None else 1.0)
 
+    def outputs(self):
+        """what the last step left for its caller: the three tapped tensors, and the weights, gradients and BatchNorm moving
+        statistics after the update"""
+        out = {t.name: self.eng.output(i) for i, t in enumerate(self.model.outputs)}
+        return dict(out, **trained_state(self.eng))
+
+
+def trained_state(eng):
+    P = eng.P
+    return {"params": P["params"].download(), "grads": P["grads"].download(), "state": P["state"].download()}
+
 
 class FullStep:
     """configs[2]: encode targets -> forward -> 3 losses -> backward (-> all-reduce) -> Adam"""
@@ -182,6 +195,16 @@ class FullStep:
         if self.reducer is not None:
             self.reducer()
         e.adam_step(lr=1e-4, grad_scale=self.reducer.scale if self.reducer is not None else 1.0)
+
+    def outputs(self):
+        """what the last step left for its caller: the Keras-named batch losses, the detection heads' outputs (class
+        probabilities, box offsets; the mask probabilities are never materialised -- the loss is fused into the mask head), and
+        the weights, gradients and BatchNorm moving statistics after the update"""
+        out = {k: np.float64(v) for k, v in self.eng.losses().items()}
+        for i, t in enumerate(self.model.outputs):
+            if t.name != "output-mask":
+                out[t.name] = self.eng.output(i)
+        return dict(out, **trained_state(self.eng))
 
 
 class ShuffleNetStep(FullStep):
@@ -339,6 +362,30 @@ def nms_boxes_per_sec(ctx, batch, reps=20):
                     f"value = the reference's thresholds (NB03#cell23)", "reference_thresholds": ref, "stress_thresholds": stress}
 
 
+DUMP_WHOLE_ELEMS = 1 << 22       # arrays up to this size are written whole (the 4,009,920 weights of the full model among them) ...
+DUMP_SAMPLE_ELEMS = 1 << 20      # ... larger ones as this many elements at fixed, seeded positions of the flattened array
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outputs: dict, out_dir: str) -> None:
+    """outputs -> out_dir/<name>.npy (float32, or float64 for the losses).  An array of more than DUMP_WHOLE_ELEMS elements is
+    written as `a.reshape(-1)[idx]`, idx = sorted(default_rng(1993).integers(0, a.size, DUMP_SAMPLE_ELEMS)): the same positions
+    in every run of the same workload, so two builds compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.size > DUMP_WHOLE_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(1993).integers(0, a.size, DUMP_SAMPLE_ELEMS))]
+        arrays[name] = a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(n: int) -> int:
     """`python bench.py --gpus N` with no launcher around it: start N FRESH rank processes of this same script (one per GPU;
     RANK / LOCAL_RANK / WORLD_SIZE and a private rendezvous path in their environment), relay rank 0's JSON line, return
@@ -390,10 +437,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch")
     ap.add_argument("--workload", default="full", choices=list(STEPS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="do not bracket kernels with HIP events in the timed region")
-    ap.add_argument("--all-kernels", action="store_true", help="list every kernel symbol of the survey step (default: the 16 heaviest)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel survey + roofline, decode + NMS boxes/sec and the NumPy CPU baseline (each outside the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: do not bracket kernels with HIP events in the timed region")
+    ap.add_argument("--all-kernels", action="store_true", help="with --full: list every kernel symbol of the survey step (default: the 16 heaviest)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    kernel_timing = args.full and not args.no_kernel_timing
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # nobody launched the ranks for us: this process becomes the launcher -- BEFORE anything here touches HIP
@@ -428,7 +481,7 @@ def main():
         step()
     barrier()
     survey, dominant = {}, None
-    if not args.no_kernel_timing:
+    if kernel_timing:
         # one untimed, fully instrumented step (every launch bracketed by HIP events) to rank the kernels ...
         # (the survey runs WITHOUT the side stream: with weight-gradient kernels co-running, per-kernel durations include each
         # other's interference and the ranking would pick whatever happened to be stretched most)
@@ -450,7 +503,9 @@ def main():
     ctx.sync()
     elapsed = time.perf_counter() - t0
     barrier()
-    report = ctx.timing_report() if not args.no_kernel_timing else {}
+    report = ctx.timing_report() if kernel_timing else {}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step.outputs(), args.dump_outputs)      # before anything below runs the step again
     # The timed region runs weight-gradient kernels on a side stream, so the dominant kernel's HIP-event duration above includes
     # whatever co-ran with it.  A few extra steps WITHOUT the side stream give the same kernel's stand-alone duration; reported
     # as `roofline_isolated` next to (never instead of) the timed-region `roofline`.
@@ -556,9 +611,9 @@ def main():
                  "GB/s": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else 0.0,
                  "TFLOP/s": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] > 0 else 0.0} for k, v in top]
             out["kernel_ms_per_step"] = round(total_ms, 3)
-        if world == 1 and args.workload != "backbone":
+        if args.full and world == 1 and args.workload != "backbone":
             out["nms_boxes_per_sec"] = nms_boxes_per_sec(ctx, args.batch)   # the metric's second figure (outside the timed region)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, 12 if args.workload == "backbone" else 6)   # ~10-30 s of host work (6.5 s per 3 images of the full step on the GPU box)
         print(json.dumps(out), flush=True)
 

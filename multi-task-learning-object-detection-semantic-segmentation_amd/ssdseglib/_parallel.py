@@ -94,9 +94,12 @@ def _read(path: str) -> bytes:
 
 
 def rendezvous_cleanup(path: str) -> None:
-    """remove the files of a (finished or crashed) rendezvous on `path`"""
+    """remove the files of a (finished or crashed) rendezvous on `path`.  Only `path.ack<rank>` itself: a rank that is
+    acknowledging a stale id at this moment owns `path.ack<rank>.<pid>.tmp` until its rename, and must keep it."""
     import glob
-    for p in [path, path + ".go"] + glob.glob(glob.escape(path) + ".ack*"):
+    import re
+    acks = [p for p in glob.glob(glob.escape(path) + ".ack*") if re.fullmatch(r"\d+", p[len(path) + 4:])]
+    for p in [path, path + ".go"] + acks:
         try:
             os.unlink(p)
         except OSError:

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/slab
 mkdir -p $OUT
 for f in 0.5 0.25 0.125 1.0; do
-  SSDSEG_WGRAD_SLAB_FRAC=$f timeout -k 10 300 python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --all-kernels > $OUT/bench_$f.json 2> $OUT/bench_$f.err
+  SSDSEG_WGRAD_SLAB_FRAC=$f timeout -k 10 300 python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --all-kernels > $OUT/bench_$f.json 2> $OUT/bench_$f.err
   python3 - $OUT/bench_$f.json $f <<'PY' | tee -a $OUT/summary.txt
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_BUSY_CYCLES SQ_WAVES \
-    --kernel-trace --output-format csv -d $OUT/sq -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline "$@" > $OUT/sq.log 2>&1 || { tail -5 $OUT/sq.log; exit 1; }
+    --kernel-trace --output-format csv -d $OUT/sq -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "$@" > $OUT/sq.log 2>&1 || { tail -5 $OUT/sq.log; exit 1; }
 python3 - "$OUT" <<'EOF'
 import collections, csv, glob, re, sys
 out = sys.argv[1]

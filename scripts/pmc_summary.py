@@ -5,8 +5,8 @@ usage: python scripts/pmc_summary.py <fetch_dir> <write_dir> <out.json>
 
 Collected with (one pass per counter, --kernel-trace only, as /opt/skills/guides/MI355X_MICROARCH.md prescribes):
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d <fetch_dir> -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d <write_dir> -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d <fetch_dir> -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d <write_dir> -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
 
 Units and the gfx950 correction (same guide, "HBM" section): the counters are in KiB-like units of 1024 B; FETCH_SIZE
 tallies each 128-B request of a wide (16 B / lane) streaming read as 64 B, so it is DOUBLED here (all the streaming kernels

@@ -206,6 +206,20 @@ def test_rendezvous_handshake_ignores_stale_files_and_times_out(tmp_path):
         P.exchange_bytes(0, fresh, 128, str(tmp_path / "other"), timeout_s=0.3, world=2)
 
 
+def test_rendezvous_cleanup_spares_an_acknowledgement_being_written(tmp_path):
+    """rank 0 clears the files of an earlier launch while a rank > 0 may be acknowledging the stale id: that rank's private
+    `ack<k>.<pid>.tmp` must survive until its rename, or the rename fails (FileNotFoundError) and the rank dies"""
+    from ssdseglib import _parallel as P
+    path = str(tmp_path / "rdzv")
+    for name in ("rdzv", "rdzv.go", "rdzv.ack1", "rdzv.ack12"):
+        (tmp_path / name).write_bytes(b"S" * 32)
+    in_flight = tmp_path / "rdzv.ack1.4242.tmp"
+    in_flight.write_bytes(b"S" * 32)
+    P.rendezvous_cleanup(path)
+    assert sorted(p.name for p in tmp_path.iterdir()) == [in_flight.name]
+    os.replace(in_flight, path + ".ack1")                 # the writer's rename (_publish) then completes
+
+
 def test_unknown_transport_and_missing_dir_are_errors(monkeypatch):
     from ssdseglib import _parallel as P
     monkeypatch.setenv("WORLD_SIZE", "2")
