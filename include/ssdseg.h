@@ -380,6 +380,15 @@ int ssdseg_expand_inputs(ssdseg_ctx* ctx, const uint8_t* images_u8, const uint8_
                          float* mask_onehot, int b, int h, int w, int c);
 /* gt [b][gmax][5] = (label, xmin, ymin, xmax, ymax), in place, rows g < gt_count[n] of the samples with flip[n] != 0 */
 int ssdseg_flip_gt_boxes(ssdseg_ctx* ctx, float* gt, const int32_t* gt_count, const uint8_t* flip, int b, int gmax, float image_width);
+/* DataEncoderDecoder.augmentation_rgb_channels (datacoder.py:434-466) on the compact pixels, as the host spec
+ * datacoder._augment_rgb: hue shift, saturation scale, contrast about the per-(image, channel) mean of the hue- and
+ * saturation-adjusted image, brightness shift (the [0, 1]-scale deltas on 0..255 values, quirk Q11), clip to [0, 255].
+ * draws4_host = (hue_delta, saturation_factor, contrast_factor, brightness_delta): ONE set for the whole batch, as
+ * tf.image.random_* draw one scalar per call on a 4-D tensor.  images_u8 [b][h][w][3]; flip [b] or NULL (mirror the
+ * flagged images left-right, as ssdseg_expand_inputs does); means [b][3] (device, out); images_f32 [b][h][w][3] (out).
+ * The means are reduced in a fixed order (block partials in the ctx workspace): the result is the same bits on every run. */
+int ssdseg_rgb_augment(ssdseg_ctx* ctx, const uint8_t* images_u8, const uint8_t* flip, const float* draws4_host,
+                       float* means, float* images_f32, int b, int h, int w);
 
 /* ---------------------------------------------------------------- training metrics
  * Per-image values of the three metric factories NB03#cell14 passes to compile(metrics=...); Keras averages them.

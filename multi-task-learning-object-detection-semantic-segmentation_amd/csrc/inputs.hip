@@ -11,6 +11,15 @@
 //   ssdseg_flip_gt_boxes   mirrors the ground-truth rows of the flagged samples (xmin' = W - xmax, xmax' = W - xmin :202-203),
 // after which ssdseg_encode_targets (boxes.hip) runs on the device as before.  Byte / integer work throughout: results are
 // bit-identical to the host path (tests/test_gpu_input_pipeline.py).
+// And DataEncoderDecoder.augmentation_rgb_channels (reference datacoder.py:434-466), the colour step the reference maps over every
+// batch after read_and_encode, on the same compact pixels:
+//   ssdseg_rgb_augment     hue shift, saturation scale (two RGB->HSV->RGB round trips), contrast about the per-(image, channel)
+//                          mean, brightness shift and the clip to [0, 255] -- with ONE draw set for the batch -- from the uint8
+//                          pixels straight into the engine's float32 input buffer, mirrored where flagged.  Float work: it follows
+//                          the host spec datacoder._augment_rgb operation for operation (no FMA contraction, correctly rounded
+//                          divisions), so it agrees with it to rounding (tests/test_gpu_rgb_augmentation.py).
+#include <cmath>
+
 #include "common.h"
 
 namespace {
@@ -54,6 +63,165 @@ __global__ void flip_gt_boxes_kernel(float* __restrict__ gt, const int* __restri
     r[3] = width - xmin;
 }
 
+// ---------------------------------------------------------------- colour augmentation (datacoder._augment_rgb)
+// NumPy's float `x % 1.0` (fmod, then + 1 for a negative remainder; a zero remainder is +0): x - trunc(x) IS fmod(x, 1) exactly
+__device__ __forceinline__ float pymod1(float x) {
+    float r = x - truncf(x);
+    if (r < 0.f) r += 1.f;
+    return r == 0.f ? 0.f : r;
+}
+
+// datacoder._rgb_to_hsv on one pixel (h in [0, 1], s in [0, 1], v = max)
+__device__ __forceinline__ void rgb_to_hsv(float r, float g, float b, float& h, float& s, float& v) {
+#pragma clang fp contract(off)
+    const float mx = fmaxf(fmaxf(r, g), b), mn = fminf(fminf(r, g), b), d = mx - mn;
+    s = mx > 0.f ? d / mx : 0.f;
+    const float dd = d > 0.f ? d : 1.f;
+    const float hh = mx == r ? (g - b) / dd : (mx == g ? 2.f + (b - r) / dd : 4.f + (r - g) / dd);
+    h = d > 0.f ? pymod1(hh / 6.f) : 0.f;
+    v = mx;
+}
+
+// datacoder._hsv_to_rgb: channel = v - v*s*clip(min(k, 4 - k), 0, 1), k = (n + 6h) mod 6 for n = 5, 3, 1.  n + 6h lies in
+// [1, 11], where the mod is one exact subtraction.
+__device__ __forceinline__ float hsv_channel(float n, float dh, float s, float v) {
+#pragma clang fp contract(off)
+    float k = n + dh;
+    k = k >= 6.f ? k - 6.f : k;
+    const float t = fminf(fmaxf(fminf(k, 4.f - k), 0.f), 1.f);
+    return v - v * s * t;
+}
+
+// hue shift then saturation scale: the image whose per-channel mean the contrast step centres on
+__device__ __forceinline__ void hue_saturation(float& r, float& g, float& b, float hue, float sat) {
+#pragma clang fp contract(off)
+    float h, s, v;
+    rgb_to_hsv(r, g, b, h, s, v);
+    h = pymod1(h + hue);
+    float dh = h * 6.f;
+    r = hsv_channel(5.f, dh, s, v); g = hsv_channel(3.f, dh, s, v); b = hsv_channel(1.f, dh, s, v);
+    rgb_to_hsv(r, g, b, h, s, v);
+    s = fminf(fmaxf(s * sat, 0.f), 1.f);
+    dh = h * 6.f;
+    r = hsv_channel(5.f, dh, s, v); g = hsv_channel(3.f, dh, s, v); b = hsv_channel(1.f, dh, s, v);
+}
+
+__device__ __forceinline__ float contrast_brightness(float q, float m, float con, float bri) {
+#pragma clang fp contract(off)
+    return fminf(fmaxf((q - m) * con + m + bri, 0.f), 255.f);
+}
+
+constexpr int AUG_THREADS = 256, AUG_PIX = 4;      // 4 pixels per thread: 12 bytes in (3 dwords), 12 floats out (3 x float4)
+constexpr int AUG_BLOCK_PIX = AUG_THREADS * AUG_PIX;
+
+// the 12 bytes of pixels [p, p + 4) of one image as 3 dwords (needs p % 4 == 0 and an image of a multiple of 4 pixels)
+__device__ __forceinline__ void load4px(const uint8_t* img, int p, float px[12]) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(img + (long long)p * 3);
+    const uint32_t a[3] = {q[0], q[1], q[2]};
+#pragma unroll
+    for (int j = 0; j < 12; ++j) px[j] = (float)((a[j >> 2] >> (8 * (j & 3))) & 0xffu);
+}
+
+// pass 1: per block and channel, the sum of the hue- and saturation-adjusted values of its (up to) 1024 pixels of image
+// blockIdx.y, in a fixed order -> part[n][blockIdx.x][3].  Reads the pixels in storage order (the mean ignores the mirror).
+// VEC: every image row holds a multiple of 4 pixels.
+template <bool VEC>
+__global__ void __launch_bounds__(AUG_THREADS) rgb_aug_stats_kernel(const uint8_t* __restrict__ img, float* __restrict__ part, int hw,
+                                                                     float hue, float sat) {
+    const int n = blockIdx.y;
+    const uint8_t* src = img + (long long)n * hw * 3;
+    const int p0 = blockIdx.x * AUG_BLOCK_PIX + threadIdx.x * AUG_PIX;
+    float acc[3] = {0.f, 0.f, 0.f};
+    if (VEC && p0 < hw) {
+        float px[12];
+        load4px(src, p0, px);
+#pragma unroll
+        for (int j = 0; j < AUG_PIX; ++j) {
+            hue_saturation(px[3 * j], px[3 * j + 1], px[3 * j + 2], hue, sat);
+            acc[0] += px[3 * j]; acc[1] += px[3 * j + 1]; acc[2] += px[3 * j + 2];
+        }
+    } else if (!VEC) {
+        for (int j = 0; j < AUG_PIX; ++j) {
+            const int p = p0 + j;
+            if (p >= hw) break;
+            float r = src[p * 3], g = src[p * 3 + 1], b = src[p * 3 + 2];
+            hue_saturation(r, g, b, hue, sat);
+            acc[0] += r; acc[1] += g; acc[2] += b;
+        }
+    }
+    __shared__ float red[AUG_THREADS / 64][3];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float t = wave_sum(acc[c]);
+        if (lane == 0) red[wv][c] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < AUG_THREADS / 64; ++k) t += red[k][threadIdx.x];
+        part[((long long)n * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = t;
+    }
+}
+
+// pass 2: means[n][c] = (sum of the nb block partials, in double, fixed order) / hw.  One wave per (channel, image).
+__global__ void __launch_bounds__(64) rgb_aug_means_kernel(const float* __restrict__ part, float* __restrict__ means, int nb, int hw) {
+    const int c = blockIdx.x, n = blockIdx.y, lane = threadIdx.x;
+    double t = 0.0;
+    for (int k = lane; k < nb; k += 64) t += (double)part[((long long)n * nb + k) * 3 + c];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+    if (lane == 0) means[n * 3 + c] = (float)(t / (double)hw);
+}
+
+// pass 3: recompute the adjusted pixel from the uint8 input, contrast about the mean, brightness, clip; output pixel x of a
+// flagged image comes from source pixel w - 1 - x
+template <bool VEC>
+__global__ void __launch_bounds__(AUG_THREADS) rgb_aug_apply_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ flip,
+                                                                     const float* __restrict__ means, float* __restrict__ out, int h, int w,
+                                                                     float hue, float sat, float con, float bri) {
+    const int n = blockIdx.y, hw = h * w;
+    const uint8_t* src = img + (long long)n * hw * 3;
+    float* dst = out + (long long)n * hw * 3;
+    const bool f = flip != nullptr && flip[n] != 0;
+    const float m0 = means[n * 3], m1 = means[n * 3 + 1], m2 = means[n * 3 + 2];
+    const int p0 = blockIdx.x * AUG_BLOCK_PIX + threadIdx.x * AUG_PIX;
+    if (VEC) {
+        if (p0 >= hw) return;
+        // the 4 output pixels share a row (w % 4 == 0); mirrored, their sources are the 4 pixels ending at w - 1 - x, reversed
+        const int y = p0 / w, x = p0 - y * w;
+        float px[12];
+        load4px(src, y * w + (f ? w - AUG_PIX - x : x), px);
+        float o[12];
+#pragma unroll
+        for (int j = 0; j < AUG_PIX; ++j) {
+            float r = px[3 * j], g = px[3 * j + 1], b = px[3 * j + 2];
+            hue_saturation(r, g, b, hue, sat);
+            const int k = f ? AUG_PIX - 1 - j : j;
+            o[3 * k] = contrast_brightness(r, m0, con, bri);
+            o[3 * k + 1] = contrast_brightness(g, m1, con, bri);
+            o[3 * k + 2] = contrast_brightness(b, m2, con, bri);
+        }
+        float* d = dst + (long long)p0 * 3;
+        st4(d, make_float4(o[0], o[1], o[2], o[3]));
+        st4(d + 4, make_float4(o[4], o[5], o[6], o[7]));
+        st4(d + 8, make_float4(o[8], o[9], o[10], o[11]));
+    } else {
+        for (int j = 0; j < AUG_PIX; ++j) {
+            const int p = p0 + j;
+            if (p >= hw) break;
+            const int y = p / w, x = p - y * w;
+            const int s = y * w + (f ? w - 1 - x : x);
+            float r = src[s * 3], g = src[s * 3 + 1], b = src[s * 3 + 2];
+            hue_saturation(r, g, b, hue, sat);
+            dst[p * 3] = contrast_brightness(r, m0, con, bri);
+            dst[p * 3 + 1] = contrast_brightness(g, m1, con, bri);
+            dst[p * 3 + 2] = contrast_brightness(b, m2, con, bri);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -82,6 +250,43 @@ int ssdseg_flip_gt_boxes(ssdseg_ctx* ctx, float* gt, const int32_t* gt_count, co
     SSDSEG_ARG(flip != nullptr, 4);
     SSDSEG_ARG(b > 0 && gmax > 0, 5);
     SSDSEG_LAUNCH(ctx, 40.0 * b * gmax, 0.0, flip_gt_boxes_kernel, dim3(cdiv(b * gmax, 256)), dim3(256), 0, gt, gt_count, flip, b, gmax, image_width);
+    SSDSEG_LAUNCH_CHECK();
+    return 0;
+}
+
+int ssdseg_rgb_augment(ssdseg_ctx* ctx, const uint8_t* images_u8, const uint8_t* flip, const float* draws4_host, float* means, float* images_f32,
+                       int b, int h, int w) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    SSDSEG_ARG(images_u8 != nullptr, 2);
+    SSDSEG_ARG(draws4_host != nullptr, 4);
+    SSDSEG_ARG(std::isfinite(draws4_host[0]) && std::isfinite(draws4_host[1]) && std::isfinite(draws4_host[2]) && std::isfinite(draws4_host[3]), 4);
+    SSDSEG_ARG(means != nullptr, 5);
+    SSDSEG_ARG(images_f32 != nullptr, 6);
+    SSDSEG_ARG(b > 0 && h > 0 && w > 0, 7);
+    // one grid row per image; in-image pixel and byte offsets in 32 bits
+    SSDSEG_ARG(b <= 65535 && (long long)h * w * 3 < (1LL << 31), 7);
+    const float hue = draws4_host[0], sat = draws4_host[1], con = draws4_host[2], bri = draws4_host[3];
+    const int hw = h * w, nb = cdiv(hw, AUG_BLOCK_PIX);
+    void* ws = nullptr;
+    int rc = ssdseg_workspace(ctx, (size_t)b * nb * 3 * sizeof(float), &ws);
+    if (rc) return rc;
+    float* part = static_cast<float*>(ws);
+    const double px = (double)b * hw;
+    // dword pixel loads and float4 stores: whole groups of 4 pixels per row and aligned buffers
+    const bool vec = w % AUG_PIX == 0 && ((uintptr_t)images_u8 & 3) == 0 && ((uintptr_t)images_f32 & 15) == 0;
+    if (vec)
+        SSDSEG_LAUNCH(ctx, 3.0 * px + 12.0 * b * nb, 0.0, rgb_aug_stats_kernel<true>, dim3(nb, b), dim3(AUG_THREADS), 0, images_u8, part, hw, hue, sat);
+    else
+        SSDSEG_LAUNCH(ctx, 3.0 * px + 12.0 * b * nb, 0.0, rgb_aug_stats_kernel<false>, dim3(nb, b), dim3(AUG_THREADS), 0, images_u8, part, hw, hue, sat);
+    SSDSEG_LAUNCH_CHECK();
+    SSDSEG_LAUNCH(ctx, 12.0 * b * nb + 12.0 * b, 0.0, rgb_aug_means_kernel, dim3(3, b), dim3(64), 0, part, means, nb, hw);
+    SSDSEG_LAUNCH_CHECK();
+    if (vec)
+        SSDSEG_LAUNCH(ctx, 15.0 * px + 12.0 * b, 0.0, rgb_aug_apply_kernel<true>, dim3(nb, b), dim3(AUG_THREADS), 0, images_u8, flip, means, images_f32,
+                      h, w, hue, sat, con, bri);
+    else
+        SSDSEG_LAUNCH(ctx, 15.0 * px + 12.0 * b, 0.0, rgb_aug_apply_kernel<false>, dim3(nb, b), dim3(AUG_THREADS), 0, images_u8, flip, means, images_f32,
+                      h, w, hue, sat, con, bri);
     SSDSEG_LAUNCH_CHECK();
     return 0;
 }

@@ -1687,7 +1687,9 @@ class _CompactLoader:
     """A `datacoder.CompactBatch` into the engine's input / target buffers (reference datacoder.py:302-347 == csrc/inputs.hip +
     ssdseg_encode_targets).  stage(): 39 MB of uint8 pixels / class indices / ground-truth rows go up on the copy stream (under
     the running step when fit overlaps); consume(): the main stream waits for them and expands -- float32 image, one-hot mask,
-    both mirrored where flagged, mirrored boxes, encoded anchors -- straight into the buffers the step reads."""
+    both mirrored where flagged, mirrored boxes, encoded anchors -- straight into the buffers the step reads.  A batch that carries
+    colour-augmentation draws (datacoder.augmentation_rgb_channels) gets its image from ssdseg_rgb_augment instead of the plain
+    cast (reference datacoder.py:434-466); the mask and the boxes are the same either way."""
 
     GMAX = 64       # ground-truth rows per image the encode kernel holds in LDS (boxes.hip)
 
@@ -1701,6 +1703,7 @@ class _CompactLoader:
         self.flip = ctx.empty(b, np.uint8)
         self.gt = ctx.empty((b, self.GMAX, 5))
         self.cnt = ctx.empty(b, np.int32)
+        self.means = ctx.empty((b, 3))      # per-(image, channel) means of the colour augmentation's contrast step
         corners = np.stack([encoder.xmin_boxes_default, encoder.ymin_boxes_default, encoder.xmax_boxes_default, encoder.ymax_boxes_default], axis=1)
         self.anchors = ctx.array(corners.astype(np.float32))
         if self.det is not None and self.anchors.shape[0] != self.det.y_boxes.shape[1]:
@@ -1712,6 +1715,7 @@ class _CompactLoader:
         if self.mask_op is not None and int(encoder.num_classes) != self.mask_op.y_true.shape[-1]:
             raise ValueError(f"encoder.num_classes = {encoder.num_classes}, the model's mask head has {self.mask_op.y_true.shape[-1]} classes")
         self.staged = None
+        self.draws = None
         self._keep = None
 
     def stage(self, cb) -> None:
@@ -1731,6 +1735,7 @@ class _CompactLoader:
         for dst, src in pairs:
             self.ctx.upload_async(dst, src, after_fence=True)
         self._keep = [src for _, src in pairs]
+        self.draws = getattr(cb, "rgb_draws", None)
         self.staged = bool(flip.any())
 
     def consume(self) -> None:
@@ -1739,8 +1744,13 @@ class _CompactLoader:
         ctx.upload_join()
         flip = self.flip if self.staged else None
         c = self.mask_op.y_true.shape[-1] if self.mask_op is not None else 1
-        ctx.call("ssdseg_expand_inputs", self.img, self.midx if self.mask_op is not None else None, flip, ins.buf,
-                 self.mask_op.y_true if self.mask_op is not None else None, b, ins.h, ins.w, c)
+        if self.draws is None:
+            ctx.call("ssdseg_expand_inputs", self.img, self.midx if self.mask_op is not None else None, flip, ins.buf,
+                     self.mask_op.y_true if self.mask_op is not None else None, b, ins.h, ins.w, c)
+        else:
+            ctx.call("ssdseg_rgb_augment", self.img, flip, (C.c_float * 4)(*self.draws), self.means, ins.buf, b, ins.h, ins.w)
+            if self.mask_op is not None:
+                ctx.call("ssdseg_expand_inputs", None, self.midx, flip, None, self.mask_op.y_true, b, ins.h, ins.w, c)
         if self.det is not None:
             if flip is not None:
                 ctx.call("ssdseg_flip_gt_boxes", self.gt, self.cnt, flip, b, self.GMAX, float(ins.w))
@@ -1748,6 +1758,7 @@ class _CompactLoader:
                      float(enc.iou_threshold), (C.c_float * 4)(*enc._stds), self.det.y_labels, self.det.y_boxes, None)
         ctx.upload_fence()                          # from here on the compact staging buffers may be overwritten
         self.staged = None
+        self.draws = None
 
 
 def _compact_loader(eng: "Engine", cb) -> _CompactLoader:
@@ -1815,15 +1826,23 @@ def run_fit(model: K.Model, data, epochs=1, validation_data=None, verbose=0) -> 
             vs: Dict[str, float] = {}
             vseen = 0
             for x, y in _batches(validation_data):
-                x = np.asarray(x, np.float32)
-                eng = eval_engine_for(model, x.shape[0])   # moving statistics, no gradient buffers (Keras test_step)
-                eng.set_input(x)
-                eng.set_targets(y)
+                if _is_compact(x):
+                    n = len(x)
+                    eng = eval_engine_for(model, n)
+                    ld = _compact_loader(eng, x)
+                    ld.stage(x)
+                    ld.consume()                    # expansion (+ colour augmentation) + anchor encoding on the device
+                else:
+                    x = np.asarray(x, np.float32)
+                    n = x.shape[0]
+                    eng = eval_engine_for(model, n)    # moving statistics, no gradient buffers (Keras test_step)
+                    eng.set_input(x)
+                    eng.set_targets(y)
                 eng.forward()
                 eng.compute_metrics()
                 for k, v in eng.losses().items():
-                    vs[k] = vs.get(k, 0.0) + v * x.shape[0]
-                vseen += x.shape[0]
+                    vs[k] = vs.get(k, 0.0) + v * n
+                vseen += n
             logs.update({f"val_{k}": v / max(vseen, 1) for k, v in vs.items()})
         for k, v in logs.items():
             hist.history.setdefault(k, []).append(v)

@@ -165,9 +165,10 @@ class CompactBatch:
     """A training batch as the files hold it: uint8 pixels (B, H, W, 3), uint8 class indices (B, H, W), per-sample ground-truth
     rows (label, xmin, ymin, xmax, ymax) and flip flags -- 39 MB instead of the 285 MB of float32 tensors at batch 32, 480x640.
     `Model.fit` / `train_on_batch` accept it in place of (images, targets): float conversion, one-hot, mirroring and the anchor
-    encoding run on the GPU (ssdseg_expand_inputs, ssdseg_flip_gt_boxes, ssdseg_encode_targets)."""
+    encoding run on the GPU (ssdseg_expand_inputs, ssdseg_flip_gt_boxes, ssdseg_encode_targets).  `augmentation_rgb_channels(cb,
+    targets)` returns a copy carrying one colour-augmentation draw set (`rgb_draws`), applied on the GPU too (ssdseg_rgb_augment)."""
 
-    def __init__(self, images_u8, mask_index_u8, ground_truth, flip, encoder: "DataEncoderDecoder"):
+    def __init__(self, images_u8, mask_index_u8, ground_truth, flip, encoder: "DataEncoderDecoder", rgb_draws=None):
         self.images = np.ascontiguousarray(images_u8, np.uint8)
         self.mask_index = np.ascontiguousarray(mask_index_u8, np.uint8)
         if self.images.ndim != 4 or self.images.shape[-1] != 3 or self.mask_index.shape != self.images.shape[:3]:
@@ -177,12 +178,33 @@ class CompactBatch:
             raise ValueError("compact batch: one ground-truth array per image")
         self.flip = None if flip is None else np.ascontiguousarray(flip, np.uint8).reshape(self.images.shape[0])
         self.encoder = encoder
+        # (hue_delta, saturation_factor, contrast_factor, brightness_delta) of augmentation_rgb_channels, applied on the device
+        # (ssdseg_rgb_augment) when the batch is expanded; None: the pixels go in as they are
+        self.rgb_draws = _check_rgb_draws(rgb_draws)
 
     def __len__(self):
         return self.images.shape[0]
 
 
+def _check_rgb_draws(draws):
+    if draws is None:
+        return None
+    try:
+        out = tuple(float(v) for v in draws)
+    except (TypeError, ValueError):
+        raise ValueError(f"rgb_draws must be None or four finite numbers, got {draws!r}") from None
+    if len(out) != 4 or not all(np.isfinite(out)):
+        raise ValueError(f"rgb_draws must be None or four finite numbers (hue, saturation, contrast, brightness), got {draws!r}")
+    return out
+
+
 _aug_rng = np.random.default_rng(1993)
+
+
+def _draw_rgb():
+    """one draw set of augmentation_rgb_channels (reference datacoder.py:452-461): (hue_delta, saturation_factor, contrast_factor,
+    brightness_delta)"""
+    return (_aug_rng.uniform(-0.05, 0.05), _aug_rng.uniform(0.95, 1.05), _aug_rng.uniform(0.90, 1.10), _aug_rng.uniform(-0.10, 0.10))
 
 
 def _rgb_to_hsv(rgb):
@@ -223,8 +245,13 @@ def _augment_rgb(x, hue_delta, saturation_factor, contrast_factor, brightness_de
 def augmentation_rgb_channels(image_batch, targets_batch):
     """random hue (+-0.05), saturation (0.95..1.05), contrast (0.9..1.1), brightness (+-0.10) then clip to [0, 255]
     (reference datacoder.py:452-464; the deltas are the [0,1]-scale ones applied to 0..255 images, quirk Q11).
-    Host-side input-pipeline step; TF's exact RNG streams are not reproduced."""
-    draws = (_aug_rng.uniform(-0.05, 0.05), _aug_rng.uniform(0.95, 1.05), _aug_rng.uniform(0.90, 1.10), _aug_rng.uniform(-0.10, 0.10))
+    One draw set per call, like tf.image.random_* on a 4-D batch; TF's exact RNG streams are not reproduced.
+    Float arrays: applied here, on the host (_augment_rgb).  A CompactBatch: returns a new CompactBatch sharing its arrays with the
+    draws attached; the loader applies them on the GPU (ssdseg_rgb_augment) when it expands the batch."""
+    draws = _draw_rgb()
+    if isinstance(image_batch, CompactBatch):
+        cb = image_batch
+        return CompactBatch(cb.images, cb.mask_index, cb.ground_truth, cb.flip, cb.encoder, rgb_draws=draws), targets_batch
     return _augment_rgb(image_batch, *draws), targets_batch
 
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """PCIe-inclusive step time of the full train step as `fit` runs it: every batch handed over as host NumPy arrays
 (images 118 MB, one-hot mask 157 MB, encoded labels/offsets 2 x 4.9 MB at batch 32), versus the resident-input step
-bench.py times.  usage: python scripts/fit_path_time.py [batch]"""
+bench.py times; and fit() on compact batches, with and without the device-side colour augmentation.
+usage: python scripts/fit_path_time.py [batch]"""
 import os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "multi-task-learning-object-detection-semantic-segmentation_amd"))
@@ -49,6 +50,22 @@ for mode in ("0", "1"):
     dtc = (time.perf_counter() - t0) / K
     print(f"fit() on COMPACT batches ({(cb.images.nbytes + cb.mask_index.nbytes) / 1e6:.0f} MB uint8 up, expansion + flip + anchor encoding on the "
           f"device), SSDSEG_FIT_OVERLAP={mode}: {dtc * 1e3:.1f} ms/step = {batch / dtc:.0f} images/sec")
+# colour augmentation (augmentation_rgb_channels on compact batches: one draw set per batch, ssdseg_rgb_augment on the device),
+# alternated with the un-augmented compact fit so that both see the same clocks; per-round ratios give the spread
+os.environ["SSDSEG_FIT_OVERLAP"] = "1"
+aug = [ssdseglib.datacoder.augmentation_rgb_channels(cb, None)[0] for _ in range(K)]
+model.fit(aug[:3], epochs=1)
+plain_t, aug_t = [], []
+for _ in range(5):
+    for data, acc in (([cb] * K, plain_t), (aug, aug_t)):
+        t0 = time.perf_counter()
+        model.fit(data, epochs=1)
+        acc.append((time.perf_counter() - t0) / K)
+ratios = [a / p - 1.0 for a, p in zip(aug_t, plain_t)]
+dta, dtp = float(np.median(aug_t)), float(np.median(plain_t))
+print(f"fit() on COMPACT batches WITH colour augmentation (hue/saturation/contrast/brightness on the device), SSDSEG_FIT_OVERLAP=1: "
+      f"{dta * 1e3:.1f} ms/step = {batch / dta:.0f} images/sec vs {dtp * 1e3:.1f} ms/step un-augmented, alternated 5 x {K} steps: "
+      f"median {100 * (dta / dtp - 1):+.2f} %, per round {min(ratios) * 100:+.2f} .. {max(ratios) * 100:+.2f} %")
 eng = E.engine_for(model, batch, True)
 t0 = time.perf_counter()
 for _ in range(K):
