@@ -102,7 +102,9 @@ int ssdseg_ctx_side_enable(ssdseg_ctx* ctx, int enabled);
  * `optimizer.apply_gradients`, NB03#cell16), so with enabled != 0 those ~80 small launches per backward pass are recorded
  * instead of launched and go out as ONE launch at the next join (ssdseg_ctx_join, and every entry point that joins: sync, copies,
  * all-reduce, Adam).  Same summation order either way: gradients are bit-identical with deferral on or off.
- * enabled == 0 flushes what is pending and returns to one launch per column sum. */
+ * enabled == 0 flushes what is pending and returns to one launch per column sum (the engine's backward pass ends that way, so an
+ * entry point called after it folds its own slabs).  Calls that keep deferral on without a join fold what is pending once the
+ * slab arena reaches SSDSEG_COLSUM_ARENA_MB (default 4096) instead of growing it further. */
 int ssdseg_colsum_defer(ssdseg_ctx* ctx, int enabled);
 int ssdseg_ctx_reserve(ssdseg_ctx* ctx, size_t workspace_bytes);
 int ssdseg_ctx_device_name(ssdseg_ctx* ctx, char* buf_host, size_t buf_len);

@@ -366,16 +366,33 @@ static bool defer_owns(const ssdseg_defer* d, const void* p) {
     return false;
 }
 
+// Arena size past which ssdseg_partials folds what is pending before it allocates more (SSDSEG_COLSUM_ARENA_MB, default 4 GiB: far
+// above what one backward pass of the engine holds, so a pass never flushes early).  Bounds a loop of weight-gradient entry points
+// called with deferral on and no join in between, whose slabs would otherwise stay allocated until the next join.
+static size_t arena_cap() {
+    const char* e = getenv("SSDSEG_COLSUM_ARENA_MB");
+    return (e != nullptr && atoll(e) > 0 ? (size_t)atoll(e) : (size_t)4096) << 20;
+}
+
 int ssdseg_partials(ssdseg_ctx* ctx, size_t bytes, void** out) {
     ssdseg_defer* d = ctx->defer;
     if (d == nullptr || !d->on || d->hold > 0) return ssdseg_workspace(ctx, bytes, out);
     bytes = (bytes + 255) & ~(size_t)255;
-    for (auto& c : d->chunks) {
-        if (c.cap - c.used >= bytes) {
-            *out = c.base + c.used;
-            c.used += bytes;
-            return 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        size_t held = 0;
+        for (auto& c : d->chunks) {
+            if (c.cap - c.used >= bytes) {
+                *out = c.base + c.used;
+                c.used += bytes;
+                return 0;
+            }
+            held += c.cap;
         }
+        // every slab handed out so far has its column sum recorded (each entry point records it before it asks again), so a join
+        // frees the whole arena.  Only from the main stream: the join there first waits for the side stream's slabs and readers.
+        if (pass > 0 || held < arena_cap() || d->pending.empty() || ctx->side_on) break;
+        int rc = ssdseg_join(ctx);
+        if (rc) return rc;
     }
     ssdseg_defer::Chunk c;
     c.cap = bytes > ((size_t)256 << 20) ? bytes : ((size_t)256 << 20);

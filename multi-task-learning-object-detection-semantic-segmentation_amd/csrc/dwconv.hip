@@ -493,6 +493,21 @@ int dw_bwd_impl(ssdseg_ctx* ctx, const ssdseg_view* in, const float* w, const ss
 
 }  // namespace
 
+// one block per partial row of the BatchNorm statistics table: rows written by each forward kernel (0 where it cannot take the layer)
+enum { DW_FWD_MARCH_K, DW_FWD_LDS_K, DW_FWD_GATHER_K };
+static int dw_fwd_rows(int n, int h, int w, int c, int stride, int dilation, int kind) {
+    DwGeom g;
+    DwLaunch l;
+    dw_geometry(n, h, w, c, stride, dilation, &g, &l);
+    if (kind == DW_FWD_MARCH_K) {                                        // column-marching kernels
+        if ((long long)n * h * w * c >= (1LL << 30)) return 0;
+        March2Geom mg;
+        return (int)march_fwd_geometry(n, h, w, c, g.ho, g.wo, stride, &mg, dilation).grid.x;
+    }
+    if (kind == DW_FWD_LDS_K) return dilation == 1 ? (int)(stride == 1 ? lds_launch<1>(g) : lds_launch<2>(g)).grid.x : 0;   // LDS-tiled
+    return dilation > 1 ? (int)l.grid.x : 0;                                                                              // gather
+}
+
 extern "C" {
 
 int ssdseg_dwconv_parts(int n, int h, int w, int c, int stride, int dilation, int* nparts_host) {
@@ -501,17 +516,11 @@ int ssdseg_dwconv_parts(int n, int h, int w, int c, int stride, int dilation, in
     SSDSEG_ARG(stride == 1 || stride == 2, 5);
     SSDSEG_ARG(dilation >= 1 && (dilation == 1 || stride == 1), 6);
     SSDSEG_ARG(nparts_host != nullptr, 7);
-    DwGeom g;
-    DwLaunch l;
-    dw_geometry(n, h, w, c, stride, dilation, &g, &l);
-    if (dw_fwd_use_march(n, h, w, c, dilation)) {
-        March2Geom mg;
-        *nparts_host = (int)march_fwd_geometry(n, h, w, c, g.ho, g.wo, stride, &mg, dilation).grid.x;   // column-marching kernels
-    } else if (dilation == 1) {
-        *nparts_host = (int)(stride == 1 ? lds_launch<1>(g) : lds_launch<2>(g)).grid.x;                  // LDS-tiled kernels
-    } else {
-        *nparts_host = (int)l.grid.x;                                                                   // gather kernels
-    }
+    // sized for whichever forward kernel may run, whatever the dispatch switches say when the table is allocated
+    // (ssdseg_dwconv_fwd zeroes the rows the launched kernel does not write)
+    int rows = dw_fwd_rows(n, h, w, c, stride, dilation, DW_FWD_MARCH_K);
+    const int other = dw_fwd_rows(n, h, w, c, stride, dilation, dilation == 1 ? DW_FWD_LDS_K : DW_FWD_GATHER_K);
+    *nparts_host = rows > other ? rows : other;
     return 0;
 }
 
@@ -535,7 +544,15 @@ int ssdseg_dwconv_fwd(ssdseg_ctx* ctx, const ssdseg_view* in, const float* w, fl
     // algorithmic traffic: read X, write Y, read W
     const double cost_bytes = 4.0 * ((double)n * h * wdt * c + (double)n * g.ho * g.wo * c + 9.0 * c);
     const double cost_flops = 18.0 * n * g.ho * g.wo * c;
-    if (dw_fwd_use_march(n, h, wdt, c, dilation)) {
+    const bool march = dw_fwd_use_march(n, h, wdt, c, dilation);
+    if (stats != nullptr) {      // the table is sized for the largest candidate (ssdseg_dwconv_parts): the rows this launch does not write are zero
+        int nparts = 0;
+        int rc = ssdseg_dwconv_parts(n, h, wdt, c, stride, dilation, &nparts);
+        if (rc) return rc;
+        const int mine = dw_fwd_rows(n, h, wdt, c, stride, dilation, march ? DW_FWD_MARCH_K : (dilation == 1 ? DW_FWD_LDS_K : DW_FWD_GATHER_K));
+        if (nparts > mine) SSDSEG_HIP(hipMemsetAsync(stats + (size_t)mine * 2 * c, 0, (size_t)(nparts - mine) * 2 * c * sizeof(float), ctx->stream));
+    }
+    if (march) {
         March2Geom mg;
         const MarchLaunch ml = march_fwd_geometry(n, h, wdt, c, g.ho, g.wo, stride, &mg, dilation);
         { const char* e = getenv("SSDSEG_DW_FWD_DEPTH"); mg.depth2 = !(e != nullptr && e[0] == '1'); }

@@ -2205,19 +2205,49 @@ int ssdseg_stem_conv_bwd_weight(ssdseg_ctx* ctx, const float* x, const ssdseg_gv
 }
 
 // ------------------------------------------------------------------------------------------------ dense 3x3 (K6)
+// partial rows of the BatchNorm statistics table each forward kernel writes (0 where it cannot take the layer, whatever the switches)
+enum { C3_ROWA_K, C3_TILE_K, C3_WINO4_K };
+static int conv3_fwd_rows(int n, int h, int w, int cin, int cout, int kind) {
+    if (kind == C3_ROWA_K) return rowA_grid_y(n * h * w, cout);                      // implicit GEMM; tap-expanded (narrow) form
+    if (cin % C3T_KC != 0) return 0;
+    if (kind == C3_TILE_K) return conv3t_geometry(n, h, w, cout).mtiles;             // halo tiles, Winograd F(2x2): one row per 8 x 32 tile
+    Wino4Geom g;                                                                      // F(4x4): one row per block of 4x4-pixel tiles
+    if (cin % 16 != 0 || wino_lds_floats(cin) * sizeof(float) > (size_t)160 * 1024 || wino4_lds_floats(cin) * sizeof(float) > (size_t)160 * 1024 ||
+        !wino4_geometry(h, w, &g) || (long long)36 * cin * cdiv(cout, W4_NT) * W4_NT * 4 >= (1LL << 31))
+        return 0;
+    return n * g.tiles_h * g.tiles_w;
+}
+
+// rows the kernel that ssdseg_conv3x3_fwd / _fwd_saved_from launches under the current switches writes
+static int conv3_fwd_rows_taken(int n, int h, int w, int ldx, int cin, int cout, bool saved) {
+    if (!saved && (conv3_narrow(cin, cout) || !conv3_tile_fwd_ok(cin, cout) || !conv3_tile_fits(n, h, w, ldx)))
+        return conv3_fwd_rows(n, h, w, cin, cout, C3_ROWA_K);
+    // (halo tiles and Winograd F(2x2) share the tile grid; conv3_wino_launch hands over to F(4x4) where conv3_wino4_takes)
+    return conv3_fwd_rows(n, h, w, cin, cout, conv3_wino4_takes(n, h, w, cin, cout) ? C3_WINO4_K : C3_TILE_K);
+}
+
+// the table is sized for the largest candidate (ssdseg_conv3x3_parts): zero the rows the launched kernel does not write
+static int conv3_zero_unwritten_stats(ssdseg_ctx* ctx, float* stats, int n, int h, int w, int cin, int cout, int mine) {
+    if (stats == nullptr) return 0;
+    int nparts = 0;
+    int rc = ssdseg_conv3x3_parts(n, h, w, cin, cout, &nparts);
+    if (rc) return rc;
+    if (nparts > mine) SSDSEG_HIP(hipMemsetAsync(stats + (size_t)mine * 2 * cout, 0, (size_t)(nparts - mine) * 2 * cout * sizeof(float), ctx->stream));
+    return 0;
+}
+
 int ssdseg_conv3x3_parts(int n, int h, int w, int cin, int cout, int* nparts_host) {
     SSDSEG_ARG(n > 0 && h > 0 && w > 0, 1);
     SSDSEG_ARG(cin > 0 && cin % 4 == 0, 4);
     SSDSEG_ARG(cout > 0 && cout % 4 == 0, 5);
     SSDSEG_ARG(nparts_host != nullptr, 6);
-    // the halo-tile kernel writes one partial row per 8 x 32 pixel tile, the implicit-GEMM kernels one per row-tile slot
-    if (conv3_tile_fwd_ok(cin, cout) && conv3_wino4_takes(n, h, w, cin, cout)) {      // (one row per block of 4x4-pixel tiles)
-        Wino4Geom g;
-        wino4_geometry(h, w, &g);
-        *nparts_host = n * g.tiles_h * g.tiles_w;
-        return 0;
+    // sized for whichever forward kernel may run: the dispatch switches (SSDSEG_CONV3_*) are read again at launch time
+    int rows = 0;
+    for (int kind : {C3_ROWA_K, C3_TILE_K, C3_WINO4_K}) {
+        const int r = conv3_fwd_rows(n, h, w, cin, cout, kind);
+        if (r > rows) rows = r;
     }
-    *nparts_host = conv3_tile_fwd_ok(cin, cout) ? conv3t_geometry(n, h, w, cout).mtiles : rowA_grid_y(n * h * w, cout);
+    *nparts_host = rows;
     return 0;
 }
 
@@ -2246,19 +2276,22 @@ int ssdseg_conv3x3_fwd(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, const fl
         rc = ssdseg_pwconv_fwd(ctx, in, ldx, w2, z, nc, (int)m, cin, nc, nullptr);
         ctx->ws_reserved -= wb + zb;
         if (rc) return rc;
-        int nparts = 0;
-        ssdseg_conv3x3_parts(n, h, wdt, cin, cout, &nparts);
+        const int nparts = conv3_fwd_rows(n, h, wdt, cin, cout, C3_ROWA_K);
         const int cv = cout / 4;
         SSDSEG_ARG((long long)m * cv < (1LL << 31), 6);   // 32-bit element indices in conv3n_tapsum_kernel
+        rc = conv3_zero_unwritten_stats(ctx, stats, n, h, wdt, cin, cout, nparts);
+        if (rc) return rc;
         int blocks = stats != nullptr ? nparts : (int)((m * cv + 255) / 256 < 4096 ? (m * cv + 255) / 256 : 4096);
         SSDSEG_LAUNCH(ctx, 4.0 * m * (nc + cout), 0.0, conv3n_tapsum_kernel, dim3(blocks), dim3(256), 0, (const float*)z, y, n, h, wdt, cv, stats);
         SSDSEG_LAUNCH_CHECK();
         return 0;
     }
+    int rc = conv3_zero_unwritten_stats(ctx, stats, n, h, wdt, cin, cout, conv3_fwd_rows_taken(n, h, wdt, ldx, cin, cout, false));
+    if (rc) return rc;
     if (conv3_tile_fwd_ok(cin, cout) && conv3_tile_fits(n, h, wdt, ldx)) {
         // weights with the reduction channel contiguous: W[tap][c][n] -> Wt[tap][n][c] (2.8 MB for the decoder conv, ~3 us)
         void* ws;
-        int rc = ssdseg_workspace(ctx, (size_t)9 * cin * cout * sizeof(float), &ws);
+        rc = ssdseg_workspace(ctx, (size_t)9 * cin * cout * sizeof(float), &ws);
         if (rc) return rc;
         SSDSEG_LAUNCH(ctx, 8.0 * 9 * cin * cout, 0.0, conv3_transpose_w_kernel, dim3(cdiv(cout, 32), cdiv(cin, 32), 9), dim3(256), 0, w, (float*)ws, cin, cout);
         SSDSEG_LAUNCH_CHECK();
@@ -2318,6 +2351,8 @@ int ssdseg_conv3x3_fwd_saved_from(ssdseg_ctx* ctx, const ssdseg_view* in, int ld
     int rc = ssdseg_conv3x3_saved_floats(n, h, wdt, cin, cout, &need);
     if (rc) return rc;
     SSDSEG_ARG(need > 0, 6);     // only for shapes ssdseg_conv3x3_saved_floats reports a size for
+    rc = conv3_zero_unwritten_stats(ctx, stats, n, h, wdt, cin, cout, conv3_fwd_rows_taken(n, h, wdt, cin, cin, cout, true));
+    if (rc) return rc;
     const long long tot4 = (long long)n * (h + 2) * (wdt + 2) * ((cin - c_from) / 4);
     SSDSEG_LAUNCH(ctx, 8.0 * n * h * wdt * (cin - c_from), 0.0, conv3_pad_view_kernel, dim3((unsigned)((tot4 + 255) / 256 < 16384 ? (tot4 + 255) / 256 : 16384)), dim3(256), 0,
                   in->x, in->scale, in->shift, in->act, ldx, xsaved, n, h, wdt, cin, c_from);

@@ -1318,9 +1318,13 @@ class Engine:
             self.input_store.buf.upload(a)
 
     def forward(self):
+        trunk, det, mask, _ = self._schedule()
+        if det:
+            # a training forward leaves the detection branch running on the side stream; a second forward() before backward()
+            # (which joins) would overwrite the trunk activations and weight copies it may still read (no-op after a whole step)
+            self.ctx.join()
         self._sync_padded("p", to_bucket=False)          # padded copies of the weights <- bucket (no-op for most models)
         self._refresh_wt()                                # transposed copies of the pointwise kernels: one launch
-        trunk, det, mask, _ = self._schedule()
         for op in trunk:
             op.fwd()
         if det:
@@ -1371,6 +1375,7 @@ class Engine:
             s._materialise_pending()
         self.ctx.join()     # weight-gradient kernels on the side stream: done before anyone (optimizer, all-reduce) reads them
         self._sync_padded("g", to_bucket=True)   # gradients of zero-padded weights -> their Keras-shaped slots of the bucket
+        self.ctx.colsum_defer(False)   # deferral ends with the pass: a later entry point on this context folds its slabs at once
 
     def seed_output_grad(self, index: int, g):
         """inject dL/d(output[index]) (bench config 2 / tests): output values are the ACTIVATED tensors"""
@@ -1396,6 +1401,7 @@ class Engine:
             s._materialise_pending()
         self.ctx.join()
         self._sync_padded("g", to_bucket=True)
+        self.ctx.colsum_defer(False)
 
     def output(self, index: int) -> np.ndarray:
         """activated value of output `index` as a NumPy array (N, H, W, C) -- for tests / predict"""

@@ -39,6 +39,63 @@ def test_argument_errors_do_not_need_a_device(lib):
     assert lib.ssdseg_stem_conv_parts(2, 480, 640, 32, C.byref(out)) == 0 and out.value > 0
 
 
+# Dispatch switches the forward entry points read at LAUNCH time, with the values the parity tests give them (None: unset)
+_SWITCHES = {
+    "SSDSEG_CONV3_F4": (None, "0", "1"), "SSDSEG_CONV3_TILE": (None, "0", "1"), "SSDSEG_CONV3_WINOGRAD": (None, "0", "1"),
+    "SSDSEG_CONV3_NARROW": (None, "0", "1"), "SSDSEG_DW_FWD": (None, "lds"), "SSDSEG_DW_ATROUS": (None, "gather"),
+    "SSDSEG_DW_FWD_DEPTH": (None, "1"), "SSDSEG_STEM_DIRECT": (None, "0"), "SSDSEG_PW_TILE": (None, "0", "1"),
+    "SSDSEG_NO_WRES": (None, "1"), "SSDSEG_WRES_FORCE": (None, "1"), "SSDSEG_PW_FUSED": (None, "1"), "SSDSEG_OCC_ROWS": (None, "0"),
+    "SSDSEG_PWT_SMALL": (None, "0", "32"),
+}
+
+
+def test_bn_partial_tables_do_not_depend_on_dispatch_switches(lib, monkeypatch):
+    """The engine sizes each BatchNorm partial-statistics table ONCE (ssdseg_*_parts, at lowering), the forward entry point picks
+    its kernel from the switches on EVERY call, and each kernel writes one row per block.  So the size may not depend on any
+    switch: it is the largest row count of the kernels that can take the layer, and the forward zeroes the rows its kernel leaves
+    (a table sized under one setting and written under another would otherwise be overrun, or folded with stale rows)."""
+    import ctypes as C
+    import itertools
+    conv3 = [(2, 9, 11, 16, 32), (1, 12, 16, 304, 256), (2, 8, 8, 256, 4), (1, 5, 5, 24, 8), (1, 1, 1, 8, 8), (18, 120, 22, 256, 4),
+             (3, 14, 40, 72, 96), (2, 17, 33, 40, 200), (1, 8, 32, 12, 16), (2, 6, 64, 80, 72), (3, 2, 32, 64, 64), (5, 4, 32, 132, 72),
+             (9, 2, 32, 72, 136), (2, 13, 18, 48, 80), (32, 120, 160, 304, 256), (32, 60, 80, 304, 256)]
+    dw = [(2, 15, 20, 32, 1, 1), (2, 15, 20, 32, 2, 1), (1, 30, 40, 144, 2, 1), (2, 8, 10, 960, 1, 1), (1, 9, 7, 8, 2, 1),
+          (2, 12, 16, 64, 1, 6), (32, 30, 40, 256, 1, 12), (32, 240, 320, 96, 2, 1), (32, 240, 320, 32, 1, 1), (32, 120, 160, 256, 1, 1),
+          (32, 120, 160, 144, 2, 1), (32, 30, 40, 576, 1, 1), (3, 48, 64, 96, 2, 1)]
+    pw = [(640, 16, 96), (1000, 96, 24), (2048, 576, 160), (130, 960, 320), (2457600, 16, 96), (614400, 256, 256), (153600, 192, 32),
+          (38400, 1280, 256), (66000, 176, 72)]
+    stem = [(2, 48, 64, 32), (1, 15, 21, 24), (3, 480, 640, 32), (2, 33, 47, 40), (32, 480, 640, 32), (2, 96, 128, 24)]
+    calls = [("ssdseg_conv3x3_parts", s) for s in conv3] + [("ssdseg_dwconv_parts", s) for s in dw] + \
+            [("ssdseg_pwconv_parts", (m, n)) for m, _, n in pw] + [("ssdseg_stem_conv_parts", s) for s in stem]
+
+    def sizes():
+        out = []
+        for name, dims in calls:
+            v = C.c_int()
+            assert getattr(lib, name)(*dims, C.byref(v)) == 0, (name, dims)
+            assert v.value > 0, (name, dims)
+            out.append(v.value)
+        return out
+
+    for k in _SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    want = sizes()
+    conv3_keys = [k for k in _SWITCHES if k.startswith("SSDSEG_CONV3")]
+    settings = [dict(zip(conv3_keys, vals)) for vals in itertools.product(*(_SWITCHES[k] for k in conv3_keys))]
+    settings += [{k: v} for k in _SWITCHES if k not in conv3_keys for v in _SWITCHES[k][1:]]
+    for setting in settings:
+        for k, v in setting.items():
+            if v is None:
+                monkeypatch.delenv(k, raising=False)
+            else:
+                monkeypatch.setenv(k, v)
+        got = sizes()
+        bad = [(calls[i], want[i], got[i]) for i in range(len(calls)) if got[i] != want[i]]
+        assert not bad, (setting, bad)
+        for k in setting:
+            monkeypatch.delenv(k, raising=False)
+
+
 def test_no_gpu_means_loud_failure_not_fallback():
     """the product path must not degrade to a CPU implementation"""
     from ssdseglib import _hip
