@@ -108,6 +108,11 @@ int ssdseg_ctx_side_enable(ssdseg_ctx* ctx, int enabled);
 int ssdseg_colsum_defer(ssdseg_ctx* ctx, int enabled);
 int ssdseg_ctx_reserve(ssdseg_ctx* ctx, size_t workspace_bytes);
 int ssdseg_ctx_device_name(ssdseg_ctx* ctx, char* buf_host, size_t buf_len);
+/* Debug poison (off by default; tests only).  While on != 0: ssdseg_malloc fills every new allocation with the 32-bit word
+ * 0x7FF0DEAD (a NaN as fp32) and returns after the fill has finished; every workspace and deferred-colsum arena handout is filled
+ * with the same word on the ctx stream before the caller's kernels run.  handouts (may be NULL): number of poisoned workspace /
+ * arena handouts since the ctx was created. */
+int ssdseg_ctx_debug_poison(ssdseg_ctx* ctx, int on, long long* handouts);
 int ssdseg_malloc(ssdseg_ctx* ctx, size_t bytes, void** out_host);
 int ssdseg_free(ssdseg_ctx* ctx, void* ptr);
 int ssdseg_memcpy_h2d(ssdseg_ctx* ctx, void* dst, const void* src_host, size_t bytes);

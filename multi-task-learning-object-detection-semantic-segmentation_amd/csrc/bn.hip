@@ -384,7 +384,7 @@ int ssdseg_partials(ssdseg_ctx* ctx, size_t bytes, void** out) {
             if (c.cap - c.used >= bytes) {
                 *out = c.base + c.used;
                 c.used += bytes;
-                return 0;
+                return ssdseg_poison_region(ctx, *out, bytes);
             }
             held += c.cap;
         }
@@ -402,7 +402,7 @@ int ssdseg_partials(ssdseg_ctx* ctx, size_t bytes, void** out) {
     c.base = (char*)p;
     d->chunks.push_back(c);
     *out = p;
-    return 0;
+    return ssdseg_poison_region(ctx, p, bytes);
 }
 
 static int colsum_rc(int nparts, long long len) {

@@ -41,7 +41,17 @@ struct ssdseg_ctx {
     int comm_rank, comm_world;
     // deferred column sums of weight-gradient partial slabs (bn.hip: ssdseg_colsum_defer / ssdseg_colsum_flush)
     struct ssdseg_defer* defer;
+    // debug poison (ssdseg_ctx_debug_poison, off by default): fresh allocations and every workspace / arena handout start as
+    // SSDSEG_POISON_WORD, so a kernel that leaves part of its output or of its partial table unwritten shows NaN instead of the
+    // previous call's right answer
+    bool poison;
+    long long poison_handouts;
 };
+
+#define SSDSEG_POISON_WORD 0x7FF0DEADu   // a NaN as fp32, an implausible index as int32
+
+// debug poison of a scratch region just handed out (a no-op unless ctx->poison): fills [p, p + bytes) on the ctx stream
+int ssdseg_poison_region(ssdseg_ctx* ctx, void* p, size_t bytes);
 
 extern "C" {
 bool ssdseg_side_begin(ssdseg_ctx* ctx);   // true when launches are now redirected to the side stream

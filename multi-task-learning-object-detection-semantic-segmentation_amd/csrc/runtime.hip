@@ -40,6 +40,23 @@ int ssdseg_workspace(ssdseg_ctx* ctx, size_t bytes, void** out) {
         ctx->workspace_bytes = want;
     }
     *out = (char*)ctx->workspace + ctx->ws_reserved;
+    if (ctx->poison) return ssdseg_poison_region(ctx, *out, bytes - ctx->ws_reserved);
+    return 0;
+}
+
+// Ordered on ctx->stream (the side stream while it is active), so the fill lands before the caller's kernels and after every
+// earlier reader of the region on that stream.
+int ssdseg_poison_region(ssdseg_ctx* ctx, void* p, size_t bytes) {
+    if (!ctx->poison || bytes < 4) return 0;
+    SSDSEG_HIP(hipMemsetD32Async((hipDeviceptr_t)p, (int)SSDSEG_POISON_WORD, bytes / 4, ctx->stream));
+    ctx->poison_handouts++;
+    return 0;
+}
+
+int ssdseg_ctx_debug_poison(ssdseg_ctx* ctx, int on, long long* handouts) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    ctx->poison = on != 0;
+    if (handouts) *handouts = ctx->poison_handouts;
     return 0;
 }
 
@@ -222,6 +239,8 @@ int ssdseg_ctx_create(int device, void* stream, ssdseg_ctx** out_host) {
     c->comm_rank = 0;
     c->comm_world = 1;
     c->defer = nullptr;
+    c->poison = false;
+    c->poison_handouts = 0;
     if (stream) {
         c->stream = (hipStream_t)stream;
         c->owns_stream = false;
@@ -382,6 +401,11 @@ int ssdseg_malloc(ssdseg_ctx* ctx, size_t bytes, void** out_host) {
     *out_host = nullptr;
     if (bytes == 0) return 0;
     SSDSEG_HIP(hipMalloc(out_host, bytes));
+    if (ctx->poison && bytes >= 4) {
+        // synchronous: upload_async fills fresh buffers from the copy stream, which must not race this fill
+        SSDSEG_HIP(hipMemsetD32Async((hipDeviceptr_t)*out_host, (int)SSDSEG_POISON_WORD, bytes / 4, ctx->stream));
+        SSDSEG_HIP(hipStreamSynchronize(ctx->stream));
+    }
     return 0;
 }
 

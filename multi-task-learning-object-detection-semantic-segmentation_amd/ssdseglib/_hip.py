@@ -50,6 +50,7 @@ _SIGNATURES = {
     "ssdseg_ctx_side_wait_mark": [_vp],
     "ssdseg_colsum_defer": [_vp, _i],
     "ssdseg_ctx_reserve": [_vp, _sz],
+    "ssdseg_ctx_debug_poison": [_vp, _i, C.POINTER(C.c_longlong)],
     "ssdseg_ctx_device_name": [_vp, C.c_char_p, _sz],
     "ssdseg_malloc": [_vp, _sz, C.POINTER(_vp)],
     "ssdseg_free": [_vp, _vp],
@@ -319,6 +320,7 @@ class Context:
         self.lib = load_library()
         self.handle = None
         self.allocated_bytes = 0
+        self.poison = False
         out = C.c_void_p()
         _check(self.lib.ssdseg_ctx_create(int(device), C.c_void_p(stream) if stream else None, C.byref(out)), "ssdseg_ctx_create")
         self.handle = out.value
@@ -375,6 +377,14 @@ class Context:
 
     def reserve(self, nbytes: int):
         _check(self.lib.ssdseg_ctx_reserve(self.handle, int(nbytes)), "ssdseg_ctx_reserve")
+
+    def debug_poison(self, on: bool) -> int:
+        """debug poison switch (include/ssdseg.h): new allocations and workspace / arena handouts start as 0x7FF0DEAD (NaN);
+        returns the number of poisoned handouts so far"""
+        n = C.c_longlong()
+        _check(self.lib.ssdseg_ctx_debug_poison(self.handle, 1 if on else 0, C.byref(n)), "ssdseg_ctx_debug_poison")
+        self.poison = bool(on)
+        return int(n.value)
 
     def device_name(self) -> str:
         buf = C.create_string_buffer(256)

@@ -333,3 +333,49 @@ def test_no_register_soffset_store_data_hazard_in_the_built_library():
     stores, findings = mod.scan(_hip.library_path())
     assert stores > 0, "the scan found no wide buffer store at all: has the disassembly format changed?"
     assert not findings, findings
+
+
+_GUARDED_MODULES = ("test_gpu_conv_ops", "test_gpu_head_ops", "test_gpu_baseline_shapes", "test_gpu_shufflenet_baseline",
+                    "test_gpu_input_pipeline", "test_gpu_rgb_augmentation", "test_gpu_metrics")
+
+
+def test_kernel_parity_modules_allocate_only_guarded_buffers():
+    """the kernel parity modules take every output from tests/_guard.py (poisoned body, checked guards), none from ctx.empty"""
+    here = os.path.dirname(os.path.abspath(__file__))
+    for mod in _GUARDED_MODULES:
+        src = open(os.path.join(here, mod + ".py")).read()
+        assert "ctx.empty(" not in src, f"{mod}: unguarded output buffer (use guards.out)"
+        assert "from _guard import" in src, mod
+
+
+def test_guard_reporting_on_hand_made_arrays():
+    import _guard as G
+    guard = G.pattern_bytes(G.GUARD_WORD, 64)
+    assert G.first_mismatch(guard, guard) is None
+    hit = guard.copy()
+    hit[8:16] = 0                                   # words 2 and 3
+    hit[61] = 1                                     # word 15
+    assert G.first_mismatch(hit, guard) == (2, 3)
+    # gap columns [3, 5) of a (4, 5) pitched body: one word hit at (2, 4)
+    body = np.full((4, 5), G.BODY_WORD, np.uint32)
+    body[:, 3:] = G.GUARD_WORD
+    assert G.gap_hits(body, 3, G.GUARD_WORD) == []
+    body[2, 4] = 0
+    body[1, 1] = 7                                  # a body element: not a gap hit
+    assert G.gap_hits(body, 3, G.GUARD_WORD) == [(2, 4)]
+    # unwritten: float32, int32 and uint8 views of the body pattern
+    y = np.arange(12, dtype=np.float32).reshape(3, 4)
+    y.view(np.uint32)[2, 1] = G.BODY_WORD
+    y.view(np.uint32)[0, 3] = G.BODY_WORD
+    assert G.unwritten_indices(y).tolist() == [[0, 3], [2, 1]]
+    assert G.unwritten_indices(y.view(np.int32)).tolist() == [[0, 3], [2, 1]]
+    u8 = np.zeros(10, np.uint8)
+    u8[5] = G.pattern_bytes(G.BODY_WORD, 6)[5]      # the pattern byte at offset 5
+    u8[6] = G.pattern_bytes(G.BODY_WORD, 6)[5]      # the same byte at the wrong offset: written
+    assert G.unwritten_indices(u8).tolist() == [[5]]
+    assert np.isnan(np.uint32(G.BODY_WORD).view(np.float32)) and np.isnan(np.uint32(G.INPUT_WORD).view(np.float32))
+    t = np.ones((5, 2, 3), np.float32)
+    G.assert_finite_rows(t)
+    t[3, 1, 2] = np.uint32(G.BODY_WORD).view(np.float32)
+    with pytest.raises(AssertionError, match="first: row 3"):
+        G.assert_finite_rows(t, "stats")

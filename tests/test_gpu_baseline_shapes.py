@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from oracle import np_ops as O
+from _guard import assert_finite_rows, guards  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -94,16 +95,16 @@ PW_BASELINE = [
 
 
 @pytest.mark.parametrize("m,k,n", PW_BASELINE)
-def test_pointwise_at_baseline_shape(ctx, m, k, n):
+def test_pointwise_at_baseline_shape(ctx, guards, m, k, n):
     from ssdseglib import _hip as H
     rng = np.random.default_rng(m + k + n)
     x, sc, sh = view_inputs(rng, (m, k))
     wgt = (rng.normal(0, 1, (k, n)) / np.sqrt(k)).astype(np.float32)
     w64 = wgt.astype(np.float64)
-    dx_, dsc, dsh, dw_ = ctx.array(x), ctx.array(sc), ctx.array(sh), ctx.array(wgt)
-    dy_ = ctx.empty((m, n))
+    dx_, dsc, dsh, dw_ = guards.inp(x), guards.inp(sc), guards.inp(sh), guards.inp(wgt)
+    dy_ = guards.out((m, n))
     nparts = ctx.parts("ssdseg_pwconv_parts", m, n)
-    stats = ctx.empty((nparts, 2, n))
+    stats = guards.out((nparts, 2, n))
     ctx.call("ssdseg_pwconv_fwd", H.view(dx_, dsc, dsh, RELU6), k, dw_, dy_, n, m, k, n, stats)
     y = dy_.download()
     rows = sample_rows(rng, m, 4096)
@@ -113,6 +114,7 @@ def test_pointwise_at_baseline_shape(ctx, m, k, n):
     assert np.abs(y[rows] - y_s).max() < 2e-5 * scale_y
     # BatchNorm partial sums: (a) the reduction epilogue vs the fp64 sums of the device output, (b) sum(y) vs the oracle's
     # closed form colsum(a) @ W (linear), over ALL rows
+    assert_finite_rows(stats.download(), "stats")
     st = stats.download().astype(np.float64).sum(axis=0)
     y64 = y.astype(np.float64)
     assert np.abs(st[0] - y64.sum(axis=0)).max() < 1e-4 * np.abs(y64).sum(axis=0).max()
@@ -125,11 +127,11 @@ def test_pointwise_at_baseline_shape(ctx, m, k, n):
 
     # backward: dx on sampled rows, dW by exact entries + random projections
     g, yraw, gs, gt, k1, k0 = gview_inputs(rng, (m, n))
-    bufs = [ctx.array(v) for v in (g, yraw, gs, gt, k1, k0)]
+    bufs = [guards.inp(v) for v in (g, yraw, gs, gt, k1, k0)]
     gv = H.gview(*bufs, act=RELU6)
-    ddx, ddw = ctx.empty((m, k)), ctx.empty((k, n))
+    ddx, ddw = guards.out((m, k)), guards.out((k, n))
     res = randn32(rng, (m, k))
-    dres = ctx.array(res)
+    dres = guards.inp(res)
     # dx + dW in one call: the gradient view carries the conv's OWN forward output (contract of ssdseg_pwconv_bwd: the fused
     # kernel of the big expand convs recomputes y = view(in) * w instead of reading it); the incoming gradient is zeroed where
     # the pre-activation sits within 1e-4 of a threshold (a last-bit difference of a recomputed y must not flip a mask that matters)
@@ -139,7 +141,7 @@ def test_pointwise_at_baseline_shape(ctx, m, k, n):
         near[lo:lo + (1 << 18)] = (np.abs(z_own) < 1e-4) | (np.abs(z_own - 6) < 1e-4)
     g_own = np.where(near, np.float32(0), g)
     del near
-    gv_own = H.gview(ctx.array(g_own), dy_, *bufs[2:], act=RELU6)
+    gv_own = H.gview(guards.inp(g_own), dy_, *bufs[2:], act=RELU6)
     ctx.call("ssdseg_pwconv_bwd", H.view(dx_, dsc, dsh, RELU6), k, gv_own, n, dw_, ddx, k, ddw, m, k, n, dres, k, 0)
     dxg = ddx.download()
     dx_o = dy64(g_own[rows], y[rows], gs, gt, k1, k0) @ w64.T + res[rows]
@@ -151,17 +153,21 @@ def test_pointwise_at_baseline_shape(ctx, m, k, n):
     dy_s = dy64(g[rows], yraw[rows], gs, gt, k1, k0)
     dx_s = dy_s @ w64.T + res[rows]
     # the separate kernels (what the engine calls when dx is not wanted / for the BN-fused variant): they read whatever y the view holds
+    guards.check()
+    guards.repoison(ddw)
     ctx.call("ssdseg_pwconv_bwd_weight", H.view(dx_, dsc, dsh, RELU6), k, gv, n, ddw, m, k, n)
     dwg = ddw.download().astype(np.float64)
     check_wgrad(rng, dwg, lambda lo, hi: act64(x[lo:hi], sc, sh), lambda lo, hi: dy64(g[lo:hi], yraw[lo:hi], gs, gt, k1, k0), m)
+    guards.repoison(ddx)
     ctx.call("ssdseg_pwconv_bwd_data", gv, n, dw_, ddx, k, m, k, n, None, 0, 0)
     assert np.abs(ddx.download()[rows] - (dx_s - res[rows])).max() < 2e-5 * np.abs(dx_s).max()
     if k > n:
         # project convs: backward-data with the producer BatchNorm's backward sums fused into the epilogue
         mean = np.zeros(k, np.float32)
         invstd = np.ones(k, np.float32)
-        outs = [ctx.empty(k) for _ in range(4)]
-        ctx.call("ssdseg_pwconv_bwd_bn", H.view(dx_, dsc, dsh, RELU6), k, gv, n, dw_, ddx, k, ddw, m, k, n, ctx.array(mean), ctx.array(invstd), *outs)
+        outs = [guards.out(k) for _ in range(4)]
+        guards.repoison(ddx); guards.repoison(ddw)
+        ctx.call("ssdseg_pwconv_bwd_bn", H.view(dx_, dsc, dsh, RELU6), k, gv, n, dw_, ddx, k, ddw, m, k, n, guards.inp(mean), guards.inp(invstd), *outs)
         dxb = ddx.download()
         assert np.abs(dxb[rows] - (dx_s - res[rows])).max() < 2e-5 * np.abs(dx_s).max()
         dbeta = np.zeros(k)
@@ -237,23 +243,24 @@ def sample_pixels(rng, n, h, w, count):
 
 
 @pytest.mark.parametrize("n,h,w,c,s", DW_BASELINE)
-def test_depthwise_at_baseline_shape(ctx, n, h, w, c, s):
+def test_depthwise_at_baseline_shape(ctx, guards, n, h, w, c, s):
     from ssdseglib import _hip as H
     rng = np.random.default_rng(h * w + c + s)
     x, sc, sh = view_inputs(rng, (n, h, w, c))
     wgt = rng.normal(0, 0.3, (3, 3, c)).astype(np.float32)
     ho, pt, _ = O.same_pad(h, 3, s)
     wo, pl, _ = O.same_pad(w, 3, s)
-    dx_, dsc, dsh, dw_ = ctx.array(x), ctx.array(sc), ctx.array(sh), ctx.array(wgt)
-    dy_ = ctx.empty((n, ho, wo, c))
+    dx_, dsc, dsh, dw_ = guards.inp(x), guards.inp(sc), guards.inp(sh), guards.inp(wgt)
+    dy_ = guards.out((n, ho, wo, c))
     nparts = ctx.parts("ssdseg_dwconv_parts", n, h, w, c, s, 1)
-    stats = ctx.empty((nparts, 2, c))
+    stats = guards.out((nparts, 2, c))
     ctx.call("ssdseg_dwconv_fwd", H.view(dx_, dsc, dsh, RELU6), dw_, dy_, n, h, w, c, s, 1, stats)
     y = dy_.download()
     a_fn = lambda nn, hh, ww: act64(x[nn, hh, ww], sc, sh)
     opix = sample_pixels(rng, n, ho, wo, 3000)
     y_s = dw_fwd_at(a_fn, wgt, opix, s, pt, pl, h, w)
     assert np.abs(y[opix[:, 0], opix[:, 1], opix[:, 2]] - y_s).max() < 2e-5 * np.abs(y_s).max()
+    assert_finite_rows(stats.download(), "stats")
     st = stats.download().astype(np.float64).sum(axis=0)
     ysum = np.zeros(c); ysq = np.zeros(c); yabs = np.zeros(c)
     for i in range(n):
@@ -264,14 +271,14 @@ def test_depthwise_at_baseline_shape(ctx, n, h, w, c, s):
     del y
 
     g, yraw, gs, gt, k1, k0 = gview_inputs(rng, (n, ho, wo, c))
-    bufs = [ctx.array(v) for v in (g, yraw, gs, gt, k1, k0)]
+    bufs = [guards.inp(v) for v in (g, yraw, gs, gt, k1, k0)]
     gv = H.gview(*bufs, act=RELU6)
-    ddx, ddw = ctx.empty(x.shape), ctx.empty(wgt.shape)
+    ddx, ddw = guards.out(x.shape), guards.out(wgt.shape)
     mean = np.zeros(c, np.float32)
     invstd = np.ones(c, np.float32)
-    outs = [ctx.empty(c) for _ in range(4)]
+    outs = [guards.out(c) for _ in range(4)]
     # the variant the backbone runs: dx + dW + the producer BatchNorm's backward sums in one march
-    ctx.call("ssdseg_dwconv_bwd_bn", H.view(dx_, dsc, dsh, RELU6), dw_, gv, ddx, ddw, n, h, w, c, s, 1, 0, ctx.array(mean), ctx.array(invstd), *outs)
+    ctx.call("ssdseg_dwconv_bwd_bn", H.view(dx_, dsc, dsh, RELU6), dw_, gv, ddx, ddw, n, h, w, c, s, 1, 0, guards.inp(mean), guards.inp(invstd), *outs)
     dxg = ddx.download()
     dy_fn = lambda nn, hh, ww: dy64(g[nn, hh, ww], yraw[nn, hh, ww], gs, gt, k1, k0)
     ipix = sample_pixels(rng, n, h, w, 3000)
@@ -305,7 +312,7 @@ def test_depthwise_at_baseline_shape(ctx, n, h, w, c, s):
 
 # ------------------------------------------------------------------------------------------------ dense 3x3 (K6)
 @pytest.mark.parametrize("h,w", [(120, 160), (60, 80)])
-def test_conv3x3_decoder_at_baseline_shape(ctx, h, w):
+def test_conv3x3_decoder_at_baseline_shape(ctx, guards, h, w):
     """blocks.py:117 at batch 32: 32x120x160x304 -> 256 (MobileNetV2, 860.7 GFLOP per direction) and 32x60x80x304 -> 256
     (ShuffleNetV2: the decoder taps stage 2 at 60x80, models.py:748 -- the Winograd weight gradient then runs rows whose last
     32-column strip is partial: 80 = 2 * 32 + 16)"""
@@ -316,10 +323,10 @@ def test_conv3x3_decoder_at_baseline_shape(ctx, h, w):
     x, sc, sh = view_inputs(rng, (n, h, w, cin))
     wgt = (rng.normal(0, 1, (3, 3, cin, cout)) / np.sqrt(9 * cin)).astype(np.float32)
     w64 = wgt.astype(np.float64)
-    dx_, dsc, dsh, dw_ = ctx.array(x), ctx.array(sc), ctx.array(sh), ctx.array(wgt)
-    dy_ = ctx.empty((n, h, w, cout))
+    dx_, dsc, dsh, dw_ = guards.inp(x), guards.inp(sc), guards.inp(sh), guards.inp(wgt)
+    dy_ = guards.out((n, h, w, cout))
     nparts = ctx.parts("ssdseg_conv3x3_parts", n, h, w, cin, cout)
-    stats = ctx.empty((nparts, 2, cout))
+    stats = guards.out((nparts, 2, cout))
     ctx.call("ssdseg_conv3x3_fwd", H.view(dx_, dsc, dsh, RELU6), cin, dw_, dy_, n, h, w, cin, cout, stats)
     y = dy_.download()
     pix = sample_pixels(rng, n, h, w, 1500)
@@ -335,6 +342,7 @@ def test_conv3x3_decoder_at_baseline_shape(ctx, h, w):
 
     y_s = conv_at(lambda nn, hh, ww: act64(x[nn, hh, ww], sc, sh), w64, +1)
     assert np.abs(y[pix[:, 0], pix[:, 1], pix[:, 2]] - y_s).max() < 2e-5 * np.abs(y_s).max()
+    assert_finite_rows(stats.download(), "stats")
     st = stats.download().astype(np.float64).sum(axis=0)
     ysum = np.zeros(cout); ysq = np.zeros(cout); yabs = np.zeros(cout)
     for i in range(n):
@@ -347,7 +355,7 @@ def test_conv3x3_decoder_at_baseline_shape(ctx, h, w):
     # backward: the engine materialises the BatchNorm gradient view first (nine taps would each re-form it), then both kernels
     # read the identity view
     g, yraw, gs, gt, k1, k0 = gview_inputs(rng, (n, h, w, cout))
-    bufs = [ctx.array(v) for v in (g, yraw, gs, gt, k1, k0)]
+    bufs = [guards.out(g.shape).upload(g)] + [guards.inp(v) for v in (yraw, gs, gt, k1, k0)]     # g: materialised in place
     gv = H.gview(*bufs, act=RELU6)
     ctx.call("ssdseg_gview_materialize", gv, cout, m, cout)
     dy = bufs[0].download()
@@ -355,7 +363,7 @@ def test_conv3x3_decoder_at_baseline_shape(ctx, h, w):
     want = dy64(g.reshape(m, cout)[samp], yraw.reshape(m, cout)[samp], gs, gt, k1, k0)
     assert np.abs(dy.reshape(m, cout)[samp] - want).max() < 2e-5 * np.abs(want).max()
     gid = H.gview(bufs[0])
-    ddx, ddw = ctx.empty((n, h, w, cin)), ctx.empty(wgt.shape)
+    ddx, ddw = guards.out((n, h, w, cin)), guards.out(wgt.shape)
     ctx.call("ssdseg_conv3x3_bwd_data", gid, dw_, ddx, cin, n, h, w, cin, cout, 0)
     dxg = ddx.download()
     wt = np.transpose(w64, (0, 1, 3, 2))          # [kh][kw][cout][cin]
@@ -390,7 +398,7 @@ def test_conv3x3_decoder_at_baseline_shape(ctx, h, w):
 
 # ------------------------------------------------------------------------------------------------ whole step, batch 32, 480x640
 @pytest.mark.parametrize("workload", ["full", "shufflenet", "shufflenet-q1fixed"])
-def test_full_train_step_batch32_480x640_properties(ctx, workload):
+def test_full_train_step_batch32_480x640_properties(ctx, guards, workload):
     """configs[2] (MobileNetV2) and configs[4]'s per-GPU share (ShuffleNetV2-1x) in both forms SURVEY.md 8(d) allows: reference quirk
     Q1 kept (the heads' ReLU(max 0) makes every class probability 0.25, so the hard-negative pool is ONE big tie -- the selection
     is decided purely by the lowest-index-first rule, on the device and in the oracle -- and every gradient is exactly zero), and
@@ -450,8 +458,8 @@ def test_full_train_step_batch32_480x640_properties(ctx, workload):
     assert labels[..., 1:].sum() > 32
     # hard-negative mining on the device's own probabilities: the selected set equals the oracle's top-k on the same tensor
     probs = det.probs.buf.download().reshape(32, 9600, 4)
-    keep = ctx.empty(32 * 9600, np.uint8)
-    conf, loc = ctx.empty(32), ctx.empty(32)
+    keep = guards.out(32 * 9600, np.uint8)
+    conf, loc = guards.out(32), guards.out(32)
     ctx.call("ssdseg_det_loss", det.y_labels, det.probs.buf, det.y_boxes, det.boxes.buf, 32, 9600, 4, 1.0 / 32, conf, loc, None, None, keep)
     l_ref, _, keep_ref = O.confidence_loss(labels, probs)
     got_keep = keep.download()

@@ -7,8 +7,15 @@ import pytest
 from oracle import np_ops as O
 from oracle.np_model import NpModel
 from tests.test_gpu_backbone import device_relu_masks, rel
+from _guard import poisoned_ctx  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _ctx_poison(poisoned_ctx):
+    """every activation, statistics table and workspace region of the engine starts as NaN (tests/_guard.py)"""
+    return poisoned_ctx
 
 SHAPE = (96, 128, 3)
 FMAPS = ((6, 8), (3, 4), (2, 2), (1, 1))

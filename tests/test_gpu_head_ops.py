@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import np_ops as O
+from _guard import BODY_WORD, assert_finite_rows, guards  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +39,7 @@ def gview_inputs(rng, shape, act):
     return (g, y, scale, shift, k1, k0), dy.astype(np.float32)
 
 
-def test_conv3x3_wino4_plain_store_path(ctx, rng, monkeypatch):
+def test_conv3x3_wino4_plain_store_path(ctx, guards, rng, monkeypatch):
     """Outputs of 2 GiB and more leave the F(4x4, 3x3) kernel through 64-bit addresses instead of range-checked buffer stores
     (conv3_wino4.h, `accumulate == 2`); SSDSEG_W4_PLAIN_STORES=1 takes that path at a size the oracle finishes in seconds."""
     from ssdseglib import _hip as H
@@ -52,18 +53,19 @@ def test_conv3x3_wino4_plain_store_path(ctx, rng, monkeypatch):
     x, sc, sh, a = view_inputs(rng, (n, h, w, cin), act)
     wgt = (rng.normal(0, 1, (3, 3, cin, cout)) / np.sqrt(9 * cin)).astype(np.float32)
     y_ref = O.conv2d_fwd(a.astype(np.float64), wgt.astype(np.float64))
-    dx_, dsc, dsh, dw_ = ctx.array(x), ctx.array(sc), ctx.array(sh), ctx.array(wgt)
-    y = ctx.empty(y_ref.shape)
+    dx_, dsc, dsh, dw_ = guards.inp(x), guards.inp(sc), guards.inp(sh), guards.inp(wgt)
+    y = guards.out(y_ref.shape)
     nparts = ctx.parts("ssdseg_conv3x3_parts", n, h, w, cin, cout)
-    stats = ctx.empty((nparts, 2, cout))
+    stats = guards.out((nparts, 2, cout))
     ctx.call("ssdseg_conv3x3_fwd", H.view(dx_, dsc, dsh, act), cin, dw_, y, n, h, w, cin, cout, stats)
     assert rel_err(y.download(), y_ref) < 5e-5
+    assert_finite_rows(stats.download(), "conv3x3 stats")
     st = stats.download().astype(np.float64).sum(axis=0)
     assert rel_err(st[1], (y_ref ** 2).sum(axis=(0, 1, 2))) < 1e-4
     dy = rng.normal(0, 1, y_ref.shape).astype(np.float32)
     dx_ref, _, _ = O.conv2d_bwd(a.astype(np.float64), wgt.astype(np.float64), dy.astype(np.float64))
-    ddx = ctx.empty(x.shape)
-    ctx.call("ssdseg_conv3x3_bwd_data", H.gview(ctx.array(dy)), dw_, ddx, cin, n, h, w, cin, cout, 0)
+    ddx = guards.out(x.shape)
+    ctx.call("ssdseg_conv3x3_bwd_data", H.gview(guards.inp(dy)), dw_, ddx, cin, n, h, w, cin, cout, 0)
     assert rel_err(ddx.download(), dx_ref) < 5e-5
 
 
@@ -82,7 +84,7 @@ def test_conv3x3_wino4_plain_store_path(ctx, rng, monkeypatch):
 # "wino4" = forward / input gradient as Winograd F(4x4, 3x3) (conv3_wino4.h) wherever a tile geometry exists: constants up to 8 in
 # the transforms, 1.2e-5 of the output scale at 304 channels (scripts/study/winograd_f4x4_error.py) -- held to 5e-5
 @pytest.mark.parametrize("family", ["narrow", "tile", "wino", "wino4", "gemm"])
-def test_conv3x3_fwd_bwd(ctx, rng, monkeypatch, n, h, w, cin, cout, family):
+def test_conv3x3_fwd_bwd(ctx, guards, rng, monkeypatch, n, h, w, cin, cout, family):
     from ssdseglib import _hip as H
     if family == "narrow" and cout > 8:
         pytest.skip("tap-expanded form only for cout <= 8")
@@ -95,26 +97,29 @@ def test_conv3x3_fwd_bwd(ctx, rng, monkeypatch, n, h, w, cin, cout, family):
     x, sc, sh, a = view_inputs(rng, (n, h, w, cin), act)
     wgt = (rng.normal(0, 1, (3, 3, cin, cout)) / np.sqrt(9 * cin)).astype(np.float32)
     y_ref = O.conv2d_fwd(a.astype(np.float64), wgt.astype(np.float64))
-    dx_, dsc, dsh, dw_ = ctx.array(x), ctx.array(sc), ctx.array(sh), ctx.array(wgt)
-    y = ctx.empty(y_ref.shape)
+    dx_, dsc, dsh, dw_ = guards.inp(x), guards.inp(sc), guards.inp(sh), guards.inp(wgt)
+    y = guards.out(y_ref.shape)
     nparts = ctx.parts("ssdseg_conv3x3_parts", n, h, w, cin, cout)
-    stats = ctx.empty((nparts, 2, cout))
+    stats = guards.out((nparts, 2, cout))
     ctx.call("ssdseg_conv3x3_fwd", H.view(dx_, dsc, dsh, act), cin, dw_, y, n, h, w, cin, cout, stats)
     assert rel_err(y.download(), y_ref) < ctol
+    assert_finite_rows(stats.download(), "conv3x3 stats")
     st = stats.download().astype(np.float64).sum(axis=0)
     assert rel_err(st[1], (y_ref ** 2).sum(axis=(0, 1, 2))) < 1e-4
     assert np.abs(st[0] - y_ref.sum(axis=(0, 1, 2))).max() < 1e-4 * np.abs(y_ref).sum(axis=(0, 1, 2)).max()
     # forward from a channel slice of a wider input buffer (the decoder conv reads the 304-channel concat)
     ldi = cin + 8
-    xw = np.zeros((n, h, w, ldi), np.float32)
+    xw = np.full((n, h, w, ldi), np.nan, np.float32)      # the channels outside the slice: NaN, so a read of them shows
     xw[..., 4:4 + cin] = x
-    dxw = ctx.array(xw)
+    dxw = guards.inp(xw)
+    guards.check()
+    guards.repoison(y)
     ctx.call("ssdseg_conv3x3_fwd", H.view(dxw.view(4, (dxw.size - 4,)), dsc, dsh, act), ldi, dw_, y, n, h, w, cin, cout, None)
     assert rel_err(y.download(), y_ref) < ctol
     gv, dy = gview_inputs(rng, y_ref.shape, O.ACT_RELU6)
-    bufs = [ctx.array(v) for v in gv]
+    bufs = [guards.inp(v) for v in gv]
     dx_ref, dw_ref, _ = O.conv2d_bwd(a.astype(np.float64), wgt.astype(np.float64), dy.astype(np.float64))
-    ddx = ctx.empty(x.shape)
+    ddx = guards.out(x.shape)
     ctx.call("ssdseg_conv3x3_bwd_data", H.gview(*bufs, act=O.ACT_RELU6), dw_, ddx, cin, n, h, w, cin, cout, 0)
     assert rel_err(ddx.download(), dx_ref) < ctol
     base = rng.normal(0, 1, x.shape).astype(np.float32)
@@ -125,10 +130,10 @@ def test_conv3x3_fwd_bwd(ctx, rng, monkeypatch, n, h, w, cin, cout, family):
     # narrow form, conv + separate reduction otherwise -- the same numbers either way
     mean = x.mean(axis=(0, 1, 2), dtype=np.float64).astype(np.float32)
     invstd = (1.0 / np.sqrt(x.var(axis=(0, 1, 2), dtype=np.float64) + 1e-3)).astype(np.float32)
-    outs = [ctx.empty(cin) for _ in range(4)]
-    ddx.upload(base)
+    outs = [guards.out(cin) for _ in range(4)]
+    guards.repoison(ddx)       # overwritten
     ctx.call("ssdseg_conv3x3_bwd_data_bn", H.view(dx_, dsc, dsh, act), H.gview(*bufs, act=O.ACT_RELU6), dw_, ddx, cin, n, h, w, cin, cout,
-             ctx.array(mean), ctx.array(invstd), *outs)
+             guards.inp(mean), guards.inp(invstd), *outs)
     assert rel_err(ddx.download(), dx_ref) < ctol
     cnt = n * h * w
     mg = dx_ref * O.act_mask(x.astype(np.float64) * sc + sh, act)
@@ -143,66 +148,68 @@ def test_conv3x3_fwd_bwd(ctx, rng, monkeypatch, n, h, w, cin, cout, family):
     if family == "narrow" and cin == 256 and cout == 4:
         # that was the streaming kernel of csrc/conv3n.hip (default for 256 -> 4); the tap-expanded GEMM form of the same entry point:
         monkeypatch.setenv("SSDSEG_CONV3N_DIRECT", "0")
-        outs2 = [ctx.empty(cin) for _ in range(4)]
-        ddx.upload(base)
+        outs2 = [guards.out(cin) for _ in range(4)]
+        guards.repoison(ddx)
         ctx.call("ssdseg_conv3x3_bwd_data_bn", H.view(dx_, dsc, dsh, act), H.gview(*bufs, act=O.ACT_RELU6), dw_, ddx, cin, n, h, w, cin, cout,
-                 ctx.array(mean), ctx.array(invstd), *outs2)
+                 guards.inp(mean), guards.inp(invstd), *outs2)
         assert rel_err(ddx.download(), dx_ref) < ctol
         assert np.abs(outs2[0].download() - dgamma).max() < tol and np.abs(outs2[1].download() - dbeta).max() < tol
         monkeypatch.delenv("SSDSEG_CONV3N_DIRECT")
     # the engine's form: the BatchNorm gradient view materialised once, then the identity view (the halo-tile kernel's input),
     # written into a channel slice of a wider (concat) gradient buffer, overwrite and accumulate
-    dmat = ctx.array(dy)
+    dmat = guards.inp(dy)
     ldx = cin + 8
-    wide = ctx.zeros((n * h * w, ldx))
+    wide = guards.out((n * h * w, ldx))
     ctx.call("ssdseg_conv3x3_bwd_data", H.gview(dmat), dw_, wide.view(4, (wide.size - 4,)), ldx, n, h, w, cin, cout, 0)
     got = wide.download().reshape(n, h, w, ldx)
-    assert rel_err(got[..., 4:4 + cin], dx_ref) < ctol and np.all(got[..., :4] == 0) and np.all(got[..., 4 + cin:] == 0)
+    assert rel_err(got[..., 4:4 + cin], dx_ref) < ctol and np.all(got[..., :4].view(np.uint32) == BODY_WORD) and \
+        np.all(got[..., 4 + cin:].view(np.uint32) == BODY_WORD)
     ctx.call("ssdseg_conv3x3_bwd_data", H.gview(dmat), dw_, wide.view(4, (wide.size - 4,)), ldx, n, h, w, cin, cout, 1)
     assert rel_err(wide.download().reshape(n, h, w, ldx)[..., 4:4 + cin], 2 * dx_ref) < ctol
-    ddw = ctx.empty(wgt.shape)
+    ddw = guards.out(wgt.shape)
     # identity gradient view (the engine's form): the halo-tile weight-gradient kernel in the "tile" family; input read from a
     # channel slice of the wider buffer
     ctx.call("ssdseg_conv3x3_bwd_weight", H.view(dxw.view(4, (dxw.size - 4,)), dsc, dsh, act), ldi, H.gview(dmat), ddw, n, h, w, cin, cout)
     assert rel_err(ddw.download(), dw_ref) < 5e-5
-    ddw.upload(np.zeros(wgt.shape, np.float32))
+    guards.repoison(ddw)
     ctx.call("ssdseg_conv3x3_bwd_weight", H.view(dx_, dsc, dsh, act), cin, H.gview(*bufs, act=O.ACT_RELU6), ddw, n, h, w, cin, cout)
     assert rel_err(ddw.download(), dw_ref) < 5e-5      # BatchNorm gradient view: all nine taps in one pass (conv3_wgrad.h; twelve waves for cout > 32)
     monkeypatch.setenv("SSDSEG_CONV3_WGRAD", "nine")   # one wave per tap for every width
-    ddw.upload(np.zeros(wgt.shape, np.float32))
+    guards.repoison(ddw)
     ctx.call("ssdseg_conv3x3_bwd_weight", H.view(dx_, dsc, dsh, act), cin, H.gview(*bufs, act=O.ACT_RELU6), ddw, n, h, w, cin, cout)
     assert rel_err(ddw.download(), dw_ref) < 5e-5
     monkeypatch.setenv("SSDSEG_CONV3_WGRAD", "taps")   # the nine shifted weight-gradient GEMMs
-    ddw.upload(np.zeros(wgt.shape, np.float32))
+    guards.repoison(ddw)
     ctx.call("ssdseg_conv3x3_bwd_weight", H.view(dx_, dsc, dsh, act), cin, H.gview(*bufs, act=O.ACT_RELU6), ddw, n, h, w, cin, cout)
     assert rel_err(ddw.download(), dw_ref) < 5e-5
 
 
-def test_gap(ctx, rng):
+def test_gap(ctx, guards, rng):
     from ssdseglib import _hip as H
     n, h, w, c = 3, 30, 40, 576
     x, sc, sh, a = view_inputs(rng, (n, h, w, c), O.ACT_RELU6)
-    out = ctx.empty((n, c))
-    ctx.call("ssdseg_gap_fwd", H.view(ctx.array(x), ctx.array(sc), ctx.array(sh), O.ACT_RELU6), out, n, h * w, c)
+    out = guards.out((n, c))
+    ctx.call("ssdseg_gap_fwd", H.view(guards.inp(x), guards.inp(sc), guards.inp(sh), O.ACT_RELU6), out, n, h * w, c)
     assert rel_err(out.download(), O.gap_fwd(a)[:, 0, 0]) < 1e-5
     g = rng.normal(0, 1, (n, 1, 1, c)).astype(np.float32)
     base = rng.normal(0, 1, (n, h, w, c)).astype(np.float32)
-    dx = ctx.array(base)
-    ctx.call("ssdseg_gap_bwd", ctx.array(g), dx, n, h * w, c, 1)
+    dx = guards.out(base.shape).upload(base)
+    ctx.call("ssdseg_gap_bwd", guards.inp(g), dx, n, h * w, c, 1)
     assert rel_err(dx.download(), O.gap_bwd(g, h, w) + base) < 1e-6
-    ctx.call("ssdseg_gap_bwd", ctx.array(g), dx, n, h * w, c, 0)
+    guards.repoison(dx)
+    ctx.call("ssdseg_gap_bwd", guards.inp(g), dx, n, h * w, c, 0)
     assert rel_err(dx.download(), O.gap_bwd(g, h, w)) < 1e-6
 
 
 @pytest.mark.parametrize("n,h,w,c,fy,fx", [(2, 6, 8, 16, 4, 4), (2, 1, 1, 256, 30, 40), (1, 5, 7, 8, 2, 8), (1, 3, 3, 4, 1, 1), (3, 2, 1, 72, 4, 4),
                                              (2, 5, 7, 8, 4, 4), (1, 30, 40, 16, 4, 4)])
-def test_bilinear(ctx, rng, monkeypatch, n, h, w, c, fy, fx):
+def test_bilinear(ctx, guards, rng, monkeypatch, n, h, w, c, fy, fx):
     from ssdseglib import _hip as H
     if fy == 4 and fx == 4:
         # the x4 forward kernel (one input pixel's 4x4 outputs per thread, 3x3 inputs loaded once) == the general gather kernel, bit for bit
         xx, s1, s2, _ = view_inputs(rng, (n, h, w, c), O.ACT_RELU6)
-        bufs = [ctx.array(v) for v in (xx, s1, s2)]
-        o4, og = ctx.empty((n, h * 4, w * 4, c)), ctx.empty((n, h * 4, w * 4, c))
+        bufs = [guards.inp(v) for v in (xx, s1, s2)]
+        o4, og = guards.out((n, h * 4, w * 4, c)), guards.out((n, h * 4, w * 4, c))
         ctx.call("ssdseg_bilinear_fwd", H.view(*bufs, O.ACT_RELU6), c, o4, c, n, h, w, c, 4, 4)
         monkeypatch.setenv("SSDSEG_BILINEAR", "gather")
         ctx.call("ssdseg_bilinear_fwd", H.view(*bufs, O.ACT_RELU6), c, og, c, n, h, w, c, 4, 4)
@@ -211,52 +218,53 @@ def test_bilinear(ctx, rng, monkeypatch, n, h, w, c, fy, fx):
     x, sc, sh, a = view_inputs(rng, (n, h, w, c), O.ACT_RELU6)
     ref = O.bilinear_fwd(a, fy, fx)
     ldo = c + 8                                     # write into a slice of a wider (concat) buffer
-    out = ctx.zeros((n * h * fy * w * fx, ldo))
-    ctx.call("ssdseg_bilinear_fwd", H.view(ctx.array(x), ctx.array(sc), ctx.array(sh), O.ACT_RELU6), c, out.view(4, (out.size - 4,)), ldo,
+    out = guards.out((n * h * fy * w * fx, ldo))
+    ctx.call("ssdseg_bilinear_fwd", H.view(guards.inp(x), guards.inp(sc), guards.inp(sh), O.ACT_RELU6), c, out.view(4, (out.size - 4,)), ldo,
              n, h, w, c, fy, fx)
     got = out.download().reshape(n, h * fy, w * fx, ldo)
     assert np.abs(got[..., 4:4 + c] - ref).max() < 1e-5
-    assert np.all(got[..., :4] == 0) and np.all(got[..., 4 + c:] == 0)
+    assert np.all(got[..., :4].view(np.uint32) == BODY_WORD) and np.all(got[..., 4 + c:].view(np.uint32) == BODY_WORD)
     g = rng.normal(0, 1, ref.shape).astype(np.float32)
     dx_ref = O.bilinear_bwd(g.astype(np.float64), fy, fx)
-    dx = ctx.empty((n, h, w, c))
-    ctx.call("ssdseg_bilinear_bwd", ctx.array(g), c, dx, c, n, h, w, c, fy, fx, 0)
+    dx = guards.out((n, h, w, c))
+    ctx.call("ssdseg_bilinear_bwd", guards.inp(g), c, dx, c, n, h, w, c, fy, fx, 0)
     assert rel_err(dx.download(), dx_ref) < 1e-5
     if fy == 4 and fx == 4:
         # the x4 backward kernel (a 2x2 block of input pixels per thread, the 12x12 union window loaded once; odd sizes: partial
         # blocks) against the general gather kernel: same terms, another summation order
-        dg = ctx.empty((n, h, w, c))
+        dg = guards.out((n, h, w, c))
         monkeypatch.setenv("SSDSEG_BILINEAR", "gather")
-        ctx.call("ssdseg_bilinear_bwd", ctx.array(g), c, dg, c, n, h, w, c, fy, fx, 0)
+        ctx.call("ssdseg_bilinear_bwd", guards.inp(g), c, dg, c, n, h, w, c, fy, fx, 0)
         monkeypatch.delenv("SSDSEG_BILINEAR")
         assert rel_err(dg.download(), dx_ref) < 1e-5 and rel_err(dx.download(), dg.download()) < 2e-6
     base = rng.normal(0, 1, (n, h, w, c)).astype(np.float32)
     dx.upload(base)
-    ctx.call("ssdseg_bilinear_bwd", ctx.array(g), c, dx, c, n, h, w, c, fy, fx, 1)
+    ctx.call("ssdseg_bilinear_bwd", guards.inp(g), c, dx, c, n, h, w, c, fy, fx, 1)
     assert rel_err(dx.download(), dx_ref + base) < 1e-5
     # the gradient arriving as a slice of a wider (concat) gradient buffer, the result leaving into one
     gw = rng.normal(0, 1, (n * h * fy * w * fx, ldo)).astype(np.float32)
     gw[:, 4:4 + c] = g.reshape(-1, c)
-    gbuf = ctx.array(gw)
-    dxw = ctx.zeros((n * h * w, ldo))
+    gbuf = guards.inp(gw)
+    dxw = guards.out((n * h * w, ldo))
     ctx.call("ssdseg_bilinear_bwd", gbuf.view(4, (gbuf.size - 4,)), ldo, dxw.view(4, (dxw.size - 4,)), ldo, n, h, w, c, fy, fx, 0)
     got = dxw.download()
     assert rel_err(got[:, 4:4 + c].reshape(dx_ref.shape), dx_ref) < 1e-5
-    assert np.all(got[:, :4] == 0) and np.all(got[:, 4 + c:] == 0)
+    assert np.all(got[:, :4].view(np.uint32) == BODY_WORD) and np.all(got[:, 4 + c:].view(np.uint32) == BODY_WORD)
+    guards.check()
 
 
 @pytest.mark.parametrize("n,h,w,c,f,ld", [(2, 6, 8, 8, 4, 8), (3, 5, 7, 12, 4, 20), (2, 9, 4, 8, 2, 12)])
-def test_bilinear_fwd_padded(ctx, rng, n, h, w, c, f, ld):
+def test_bilinear_fwd_padded(ctx, guards, rng, n, h, w, c, f, ld):
     """the up-sampling written into the interior of a bordered tensor == the plain up-sampling, bit for bit; border and the
     channels beyond c untouched (x4 tile kernel and the general kernel)"""
     from ssdseglib import _hip as H
     x = rng.normal(0, 1, (n, h, w, c)).astype(np.float32)
     sc, sh = rng.uniform(0.5, 1.5, c).astype(np.float32), rng.normal(0, 0.3, c).astype(np.float32)
-    v = H.view(ctx.array(x), ctx.array(sc), ctx.array(sh), O.ACT_RELU6)
-    plain = ctx.empty((n, h * f, w * f, c))
+    v = H.view(guards.inp(x), guards.inp(sc), guards.inp(sh), O.ACT_RELU6)
+    plain = guards.out((n, h * f, w * f, c))
     ctx.call("ssdseg_bilinear_fwd", v, c, plain, c, n, h, w, c, f, f)
     init = rng.normal(0, 1, (n, h * f + 2, w * f + 2, ld)).astype(np.float32)
-    padded = ctx.array(init)
+    padded = guards.out(init.shape).upload(init)
     ctx.call("ssdseg_bilinear_fwd_padded", v, c, padded, ld, n, h, w, c, f, f)
     got = padded.download()
     assert np.array_equal(got[:, 1:-1, 1:-1, :c], plain.download())
@@ -267,7 +275,7 @@ def test_bilinear_fwd_padded(ctx, rng, n, h, w, c, f, ld):
 
 @pytest.mark.parametrize("n,h,w", [(2, 12, 16), (1, 17, 35), (3, 5, 3)])     # whole 16x16 tiles; ragged tiles; smaller than one tile
 @pytest.mark.parametrize("f", [4, 8])
-def test_mask_head(ctx, rng, monkeypatch, n, h, w, f):
+def test_mask_head(ctx, guards, rng, monkeypatch, n, h, w, f):
     c = 4
     logits = rng.normal(0, 2, (n, h, w, c)).astype(np.float32)
     cls = rng.integers(0, c, (n, h * f, w * f))
@@ -278,20 +286,22 @@ def test_mask_head(ctx, rng, monkeypatch, n, h, w, f):
     loss_ref, dp = O.cross_entropy_loss(y.astype(np.float64), p_ref, cw.astype(np.float64))
     dlogits_ref = O.bilinear_bwd(O.softmax_bwd(p_ref, dp * 0.5), f, f)
     cwh = (C.c_float * 4)(*cw)
-    dl, dy = ctx.array(logits), ctx.array(y)
-    prob, loss = ctx.empty(y.shape), ctx.empty(n)
+    dl, dy = guards.inp(logits), guards.inp(y)
+    prob, loss = guards.out(y.shape), guards.out(n)
     ctx.call("ssdseg_mask_head_fwd", dl, n, h, w, c, f, f, dy, cwh, prob, loss)
     assert np.abs(prob.download() - p_ref).max() < 2e-6
     assert rel_err(loss.download(), loss_ref) < 1e-5
+    guards.repoison(prob)
     ctx.call("ssdseg_mask_head_fwd", dl, n, h, w, c, f, f, None, None, prob, None)     # inference: probabilities only
     assert np.abs(prob.download() - p_ref).max() < 2e-6
-    g = ctx.empty(logits.shape)
+    g = guards.out(logits.shape)
     ctx.call("ssdseg_mask_head_bwd", dl, n, h, w, c, f, f, dy, cwh, 0.5, g)
     assert rel_err(g.download(), dlogits_ref) < 2e-5
     # the tile kernel (default for x4) computes every full-resolution dz once per block and walks each window in the order of the
     # one-thread-per-pixel kernel: bit-identical
     tile = g.download()
     monkeypatch.setenv("SSDSEG_MASK_BWD", "gather")
+    guards.repoison(g)
     ctx.call("ssdseg_mask_head_bwd", dl, n, h, w, c, f, f, dy, cwh, 0.5, g)
     if f == 4:
         np.testing.assert_array_equal(g.download(), tile)
@@ -301,7 +311,7 @@ def test_mask_head(ctx, rng, monkeypatch, n, h, w, f):
 
 @pytest.mark.parametrize("squared", [0, 1])
 @pytest.mark.parametrize("n,h,w", [(2, 6, 8), (3, 30, 40)])
-def test_mask_head_dice(ctx, rng, monkeypatch, n, h, w, squared):
+def test_mask_head_dice(ctx, guards, rng, monkeypatch, n, h, w, squared):
     """the mask head trained with the reference's dice / dice_square losses (losses.py:175-264): loss and d loss / d logits vs the
     oracle (bilinear x4 -> softmax -> dice), tile and gather backward kernels bit-identical"""
     c, f = 4, 4
@@ -314,61 +324,62 @@ def test_mask_head_dice(ctx, rng, monkeypatch, n, h, w, squared):
     assert np.allclose(loss_ref, O.dice_loss(y.astype(np.float64), p_ref, cw.astype(np.float64), squared=bool(squared)), rtol=1e-12)
     dlogits_ref = O.bilinear_bwd(O.softmax_bwd(p_ref, dp * 0.5), f, f)
     cwh = (C.c_float * 4)(*cw)
-    dl, dy = ctx.array(logits), ctx.array(y)
-    prob, loss, coef = ctx.empty(y.shape), ctx.empty(n), ctx.empty((n, 8))
+    dl, dy = guards.inp(logits), guards.inp(y)
+    prob, loss, coef = guards.out(y.shape), guards.out(n), guards.out((n, 8))
     ctx.call("ssdseg_mask_head_fwd_dice", dl, n, h, w, c, f, f, dy, cwh, squared, prob, loss, coef)
     assert np.abs(prob.download() - p_ref).max() < 2e-6
     assert rel_err(loss.download(), loss_ref) < 1e-5
-    g = ctx.empty(logits.shape)
+    g = guards.out(logits.shape)
     ctx.call("ssdseg_mask_head_bwd_dice", dl, n, h, w, c, f, f, dy, coef, squared, 0.5, g)
     assert rel_err(g.download(), dlogits_ref) < 2e-5
     tile = g.download()
     monkeypatch.setenv("SSDSEG_MASK_BWD", "gather")
+    guards.repoison(g)
     ctx.call("ssdseg_mask_head_bwd_dice", dl, n, h, w, c, f, f, dy, coef, squared, 0.5, g)
     np.testing.assert_array_equal(g.download(), tile)
     # the standalone loss function (ssdseglib.losses.dice(w)(y_true, y_pred)) agrees with the fused head
-    std = ctx.empty(n)
+    std = guards.out(n)
     ctx.call("ssdseg_dice_loss", dy, prob, n, h * f * w * f, c, cwh, squared, std)
     assert rel_err(std.download(), loss_ref) < 1e-5
 
 
-def test_head_gather_and_softmax(ctx, rng):
+def test_head_gather_and_softmax(ctx, guards, rng):
     from ssdseglib import _hip as H
     b, hw, c, off, total = 3, 20, 24, 7, 200          # 20 cells x 6 boxes x 4 values per image, placed at anchor 7
     x, sc, sh, a = view_inputs(rng, (b, hw, c), O.ACT_RELU6)
-    out = ctx.zeros((b, total, 4))
-    ctx.call("ssdseg_head_gather", H.view(ctx.array(x), ctx.array(sc), ctx.array(sh), O.ACT_RELU6), out, b, hw * c, c, off * 4, total * 4, 0)
+    out = guards.zeros((b, total, 4))
+    ctx.call("ssdseg_head_gather", H.view(guards.inp(x), guards.inp(sc), guards.inp(sh), O.ACT_RELU6), out, b, hw * c, c, off * 4, total * 4, 0)
     got = out.download()
     ref = a.reshape(b, hw * c // 4, 4)
     assert np.abs(got[:, off:off + ref.shape[1]] - ref).max() < 1e-6
     assert np.all(got[:, :off] == 0) and np.all(got[:, off + ref.shape[1]:] == 0)
-    back = ctx.empty((b, hw, c))
+    back = guards.out((b, hw, c))
     ctx.call("ssdseg_head_gather", H.view(out), back, b, hw * c, c, off * 4, total * 4, 1)
     assert np.array_equal(back.download().reshape(ref.shape), got[:, off:off + ref.shape[1]])
-    sm = ctx.empty((b, total, 4))
+    sm = guards.out((b, total, 4))
     ctx.call("ssdseg_softmax_rows", H.view(out), sm, b * total, 4)
     assert np.abs(sm.download() - O.softmax(got)).max() < 1e-6
 
 
 @pytest.mark.parametrize("n,k", [(1000, 0), (1000, 1), (5000, 1234), (307200, 2700), (4096, 4095), (4096, 4096), (10, 50),
                                  (307200, 300001), (700001, 123457), (257, 5), (1, 1)])
-def test_topk_mask_exact(ctx, rng, n, k):
+def test_topk_mask_exact(ctx, guards, rng, n, k):
     v = rng.exponential(1.0, n).astype(np.float32)
     v[rng.integers(0, n, n // 3)] = 0.0                     # plateau of ties at 0 (positives contribute 0 to the mining vector)
     v[rng.integers(0, n, n // 5)] = np.float32(0.6931472)   # plateau of ties at a positive value
     if n > 100:
         v[:7] = -1.5                                        # negative values order correctly too
-    mask = ctx.empty(n, np.uint8)
-    ctx.call("ssdseg_topk_mask", ctx.array(v), n, k, mask)
+    mask = guards.out(n, np.uint8)
+    ctx.call("ssdseg_topk_mask", guards.inp(v), n, k, mask)
     assert np.array_equal(mask.download(), O.topk_mask(v, min(k, n)))
 
 
 @pytest.mark.parametrize("n,k", [(307200, 1000), (5000, 4999), (300, 1)])
-def test_topk_mask_all_ties(ctx, n, k):
+def test_topk_mask_all_ties(ctx, guards, n, k):
     """every value equal: the selection is the k lowest indices, across block and thread boundaries of the tie pass"""
     v = np.full(n, 0.25, np.float32)
-    mask = ctx.empty(n, np.uint8)
-    ctx.call("ssdseg_topk_mask", ctx.array(v), n, k, mask)
+    mask = guards.out(n, np.uint8)
+    ctx.call("ssdseg_topk_mask", guards.inp(v), n, k, mask)
     got = mask.download()
     assert got[:k].all() and not got[k:].any()
 
@@ -384,16 +395,16 @@ def make_det_case(rng, b, a, pos_frac=0.02):
 
 
 @pytest.mark.parametrize("b,a,pos_frac", [(4, 600, 0.03), (2, 9600, 0.01), (3, 500, 0.0), (2, 300, 0.6)])
-def test_det_loss(ctx, rng, b, a, pos_frac):
+def test_det_loss(ctx, guards, rng, b, a, pos_frac):
     y, p, yb, pb = make_det_case(rng, b, a, pos_frac)
     conf_ref, dp_ref, keep_ref = O.confidence_loss(y, p)
     loc_ref, dloc_ref = O.localization_loss(yb, pb)
     scale = 1.0 / b
     dlogits_ref = O.softmax_bwd(p.astype(np.float64), dp_ref.astype(np.float64)) * scale
-    conf, loc = ctx.empty(b), ctx.empty(b)
-    dlog, dbox = ctx.empty((b, a, 4)), ctx.empty((b, a, 4))
-    keep = ctx.empty(b * a, np.uint8)
-    ctx.call("ssdseg_det_loss", ctx.array(y), ctx.array(p), ctx.array(yb), ctx.array(pb), b, a, 4, scale, conf, loc, dlog, dbox, keep)
+    conf, loc = guards.out(b), guards.out(b)
+    dlog, dbox = guards.out((b, a, 4)), guards.out((b, a, 4))
+    keep = guards.out(b * a, np.uint8)
+    ctx.call("ssdseg_det_loss", guards.inp(y), guards.inp(p), guards.inp(yb), guards.inp(pb), b, a, 4, scale, conf, loc, dlog, dbox, keep)
     # the mining key is the correctly rounded float32 log on both sides (float(log(double(p))): DESIGN.md section 4), so the
     # selected set is held bit-exact
     got_keep = keep.download()
@@ -416,7 +427,7 @@ def synthetic_gt(rng, b, gmax, hw=(480, 640)):
     return gt, cnt
 
 
-def test_encode_targets_exact(ctx, rng, golden_dir):
+def test_encode_targets_exact(ctx, guards, rng, golden_dir):
     d = np.load(f"{golden_dir}/anchors_nb03.npz")
     anchors = d["corners"]
     b, gmax = 6, 8
@@ -425,8 +436,8 @@ def test_encode_targets_exact(ctx, rng, golden_dir):
     gt[2, 1] = gt[2, 0]                                     # duplicated ground truth: arg-max ties
     gt[3, 0, 1:] = anchors[4321]                            # a box that coincides with an anchor (IoU == 1)
     stds = (0.1, 0.1, 0.2, 0.2)
-    labels, boxes, match = ctx.empty((b, 9600, 4)), ctx.empty((b, 9600, 4)), ctx.empty((b, 9600), np.int32)
-    ctx.call("ssdseg_encode_targets", ctx.array(anchors), 9600, ctx.array(gt), ctx.array(cnt), b, gmax, 4, 0.525, (C.c_float * 4)(*stds),
+    labels, boxes, match = guards.out((b, 9600, 4)), guards.out((b, 9600, 4)), guards.out((b, 9600), np.int32)
+    ctx.call("ssdseg_encode_targets", guards.inp(anchors), 9600, guards.inp(gt), guards.inp(cnt), b, gmax, 4, 0.525, (C.c_float * 4)(*stds),
              labels, boxes, match)
     L, B, M = labels.download(), boxes.download(), match.download()
     for i in range(b):
@@ -446,7 +457,7 @@ def test_encode_targets_exact(ctx, rng, golden_dir):
 
 
 @pytest.mark.parametrize("iou_thr,score_thr", [(0.025, 0.725), (0.5, 0.05), (0.3, 0.9999)])
-def test_decode_and_combined_nms_exact(ctx, rng, golden_dir, iou_thr, score_thr):
+def test_decode_and_combined_nms_exact(ctx, guards, rng, golden_dir, iou_thr, score_thr):
     d = np.load(f"{golden_dir}/anchors_nb03.npz")
     cent = d["centroids"]
     b, a, c = 4, 9600, 4
@@ -454,42 +465,42 @@ def test_decode_and_combined_nms_exact(ctx, rng, golden_dir, iou_thr, score_thr)
     probs = O.softmax((3 * rng.normal(0, 1, (b, a, c))).astype(np.float32))
     probs[3, :, 1:] = 0.0                                        # image with only background-class candidates
     stds = (0.1, 0.1, 0.2, 0.2)
-    corners = ctx.empty((b, a, 4))
-    ctx.call("ssdseg_decode_boxes", ctx.array(offsets), ctx.array(cent), b, a, (C.c_float * 4)(*stds), corners)
+    corners = guards.out((b, a, 4))
+    ctx.call("ssdseg_decode_boxes", guards.inp(offsets), guards.inp(cent), b, a, (C.c_float * 4)(*stds), corners)
     cr = corners.download()
     assert rel_err(cr, O.decode_to_corners_pred(offsets, cent, stds)) < 1e-5
-    out, valid = ctx.empty((b, 10, 6)), ctx.empty(b, np.int32)
-    ctx.call("ssdseg_combined_nms", corners, ctx.array(probs), b, a, c, 4, 10, iou_thr, score_thr, out, valid)
+    out, valid = guards.out((b, 10, 6)), guards.out(b, np.int32)
+    ctx.call("ssdseg_combined_nms", corners, guards.inp(probs), b, a, c, 4, 10, iou_thr, score_thr, out, valid)
     ref_out, ref_valid = O.combined_nms(cr, probs, 4, 10, iou_thr, score_thr)      # same decoded boxes on both sides
     assert np.array_equal(valid.download(), ref_valid)
     assert np.array_equal(out.download(), ref_out)
 
 
-def test_seg_suppress(ctx, rng):
+def test_seg_suppress(ctx, guards, rng):
     n, hw, c, rows = 2, 4800, 4, 500
     mask = O.softmax(rng.normal(0, 1, (n, hw, c)).astype(np.float32))
     mask[..., 2] = 0.0                                           # class 2 never wins anywhere in the batch
     mask[0, :10] = 0.25                                          # exact ties -> first index (class 0)
     probs = rng.uniform(0, 1, (rows, c)).astype(np.float32)
-    out = ctx.empty((rows, c))
-    ctx.call("ssdseg_seg_suppress", ctx.array(mask), n * hw, c, ctx.array(probs), rows, out)
+    out = guards.out((rows, c))
+    ctx.call("ssdseg_seg_suppress", guards.inp(mask), n * hw, c, guards.inp(probs), rows, out)
     assert np.array_equal(out.download(), O.seg_suppress(mask, probs))
     assert np.all(out.download()[:, 2] == 0)
 
 
-def test_maxpool_shuffle_actbwd_dice(ctx, rng, monkeypatch):
+def test_maxpool_shuffle_actbwd_dice(ctx, guards, rng, monkeypatch):
     from ssdseglib import _hip as H
     n, h, w, c = 2, 15, 20, 24
     x = rng.normal(0, 1, (n, h, w, c)).astype(np.float32)
     x[0, 3:6, 3:6, :] = 1.5                                      # ties inside windows
     ref = O.maxpool3x3s2_fwd(x)
-    out = ctx.empty(ref.shape)
-    dx_ = ctx.array(x)
+    out = guards.out(ref.shape)
+    dx_ = guards.inp(x)
     ctx.call("ssdseg_maxpool3x3s2_fwd", H.view(dx_), out, n, h, w, c)
     assert np.array_equal(out.download(), ref)
     g = rng.normal(0, 1, ref.shape).astype(np.float32)
-    dx = ctx.empty(x.shape)
-    ctx.call("ssdseg_maxpool3x3s2_bwd", H.view(dx_), ctx.array(g), dx, n, h, w, c)
+    dx = guards.out(x.shape)
+    ctx.call("ssdseg_maxpool3x3s2_bwd", H.view(dx_), guards.inp(g), dx, n, h, w, c)
     assert np.abs(dx.download() - O.maxpool3x3s2_bwd(x, g)).max() < 1e-6
     # the two-pass form (winner codes, default) and the one-pass window scan walk the windows in the same order: bit-identical;
     # even image sizes pad differently (SAME: (0, 1)) and a view on the input
@@ -497,39 +508,41 @@ def test_maxpool_shuffle_actbwd_dice(ctx, rng, monkeypatch):
         xx = rng.normal(0, 1, (n, hh, ww, c)).astype(np.float32)
         sc, shf = rng.uniform(0.5, 1.5, c).astype(np.float32), rng.normal(0, 1, c).astype(np.float32)
         a = np.maximum(xx * sc + shf, 0).astype(np.float32) if view else xx
-        v = H.view(ctx.array(xx), ctx.array(sc), ctx.array(shf), O.ACT_RELU) if view else H.view(ctx.array(xx))
+        v = H.view(guards.inp(xx), guards.inp(sc), guards.inp(shf), O.ACT_RELU) if view else H.view(guards.inp(xx))
         gg = rng.normal(0, 1, O.maxpool3x3s2_fwd(a).shape).astype(np.float32)
-        d1, d2 = ctx.empty(xx.shape), ctx.empty(xx.shape)
+        d1, d2 = guards.out(xx.shape), guards.out(xx.shape)
         monkeypatch.delenv("SSDSEG_MAXPOOL_BWD", raising=False)
-        ctx.call("ssdseg_maxpool3x3s2_bwd", v, ctx.array(gg), d1, n, hh, ww, c)
+        ctx.call("ssdseg_maxpool3x3s2_bwd", v, guards.inp(gg), d1, n, hh, ww, c)
         monkeypatch.setenv("SSDSEG_MAXPOOL_BWD", "scan")
-        ctx.call("ssdseg_maxpool3x3s2_bwd", v, ctx.array(gg), d2, n, hh, ww, c)
+        ctx.call("ssdseg_maxpool3x3s2_bwd", v, guards.inp(gg), d2, n, hh, ww, c)
         monkeypatch.delenv("SSDSEG_MAXPOOL_BWD", raising=False)
         assert np.array_equal(d1.download(), d2.download())
         assert np.abs(d1.download() - O.maxpool3x3s2_bwd(a, gg)).max() < 1e-5
-    sh = ctx.empty(x.shape)
+    sh = guards.out(x.shape)
     ctx.call("ssdseg_channel_shuffle", H.view(dx_), c, sh, c, n * h * w, c, 2, 0)
     assert np.array_equal(sh.download(), O.channel_shuffle(x, 2))
-    back = ctx.empty(x.shape)
+    back = guards.out(x.shape)
     ctx.call("ssdseg_channel_shuffle", H.view(sh), c, back, c, n * h * w, c, 2, 1)
     assert np.array_equal(back.download(), x)
     sc, sf = rng.uniform(0.5, 1.5, c).astype(np.float32), rng.normal(0, 0.3, c).astype(np.float32)
-    ctx.call("ssdseg_channel_shuffle", H.view(dx_, ctx.array(sc), ctx.array(sf), O.ACT_RELU), c, sh, c, n * h * w, c, 2, 0)   # fused BN + ReLU
+    guards.repoison(sh)
+    ctx.call("ssdseg_channel_shuffle", H.view(dx_, guards.inp(sc), guards.inp(sf), O.ACT_RELU), c, sh, c, n * h * w, c, 2, 0)   # fused BN + ReLU
     assert np.abs(sh.download() - O.channel_shuffle(np.maximum(x * sc + sf, 0), 2)).max() < 1e-6
-    gg = ctx.array(g_full := rng.normal(0, 1, x.shape).astype(np.float32))
+    g_full = rng.normal(0, 1, x.shape).astype(np.float32)
+    gg = guards.out(x.shape).upload(g_full)        # masked in place
     ctx.call("ssdseg_act_bwd", gg, c, dx_, c, n * h * w, c, O.ACT_RELU)
     assert np.array_equal(gg.download(), g_full * (x > 0))
     y = np.eye(4, dtype=np.float32)[rng.integers(0, 4, (n, 300))]
     p = O.softmax(rng.normal(0, 1, (n, 300, 4)).astype(np.float32))
     cw = (0.05, 0.575, 0.135, 0.24)
     for sq in (0, 1):
-        loss = ctx.empty(n)
-        ctx.call("ssdseg_dice_loss", ctx.array(y), ctx.array(p), n, 300, 4, (C.c_float * 4)(*cw), sq, loss)
+        loss = guards.out(n)
+        ctx.call("ssdseg_dice_loss", guards.inp(y), guards.inp(p), n, 300, 4, (C.c_float * 4)(*cw), sq, loss)
         assert rel_err(loss.download(), O.dice_loss(y[:, :, None], p[:, :, None], cw, bool(sq))) < 1e-5
 
 
 @pytest.mark.parametrize("n,h,w,cin,cout", [(2, 6, 64, 80, 72), (1, 16, 32, 304, 256)])
-def test_conv3x3_saved_input_pair_equals_plain_entry_points(ctx, rng, monkeypatch, n, h, w, cin, cout):
+def test_conv3x3_saved_input_pair_equals_plain_entry_points(ctx, guards, rng, monkeypatch, n, h, w, cin, cout):
     """ssdseg_conv3x3_fwd_saved / _bwd_weight_saved (the forward leaves act(BN(x)) in a zero-bordered copy, the Winograd weight
     gradient reads it again): same outputs, BatchNorm partial sums and weight gradient as the plain entry points, and the oracle's"""
     import ctypes as C
@@ -543,15 +556,17 @@ def test_conv3x3_saved_input_pair_equals_plain_entry_points(ctx, rng, monkeypatc
     need = C.c_longlong()
     assert ctx.lib.ssdseg_conv3x3_saved_floats(n, h, w, cin, cout, C.byref(need)) == 0
     assert need.value == n * (h + 2) * (w + 2) * cin
-    dx_, dsc, dsh, dw_, ddy = ctx.array(x), ctx.array(sc), ctx.array(sh), ctx.array(wgt), ctx.array(dy)
+    dx_, dsc, dsh, dw_, ddy = guards.inp(x), guards.inp(sc), guards.inp(sh), guards.inp(wgt), guards.inp(dy)
     nparts = ctx.parts("ssdseg_conv3x3_parts", n, h, w, cin, cout)
-    y0, y1 = ctx.empty((n, h, w, cout)), ctx.empty((n, h, w, cout))
-    st0, st1 = ctx.empty((nparts, 2, cout)), ctx.empty((nparts, 2, cout))
-    g0, g1 = ctx.empty(wgt.shape), ctx.empty(wgt.shape)
-    xs = ctx.empty(need.value)
+    y0, y1 = guards.out((n, h, w, cout)), guards.out((n, h, w, cout))
+    st0, st1 = guards.out((nparts, 2, cout)), guards.out((nparts, 2, cout))
+    g0, g1 = guards.out(wgt.shape), guards.out(wgt.shape)
+    xs = guards.out(need.value)
     xs.upload(np.full(need.value, np.nan, np.float32))                       # every element, borders included, must be written
     ctx.call("ssdseg_conv3x3_fwd", H.view(dx_, dsc, dsh, act), cin, dw_, y0, n, h, w, cin, cout, st0)
     ctx.call("ssdseg_conv3x3_fwd_saved", H.view(dx_, dsc, dsh, act), cin, dw_, y1, n, h, w, cin, cout, st1, xs)
+    assert_finite_rows(st0.download(), "conv3x3 stats")
+    assert_finite_rows(st1.download(), "conv3x3 saved stats")
     saved = xs.download().reshape(n, h + 2, w + 2, cin)
     assert np.abs(saved[:, 1:-1, 1:-1] - a).max() < 2e-6 * np.abs(a).max()   # act(scale * x + shift) (one fma on the device, mul + add in NumPy)
     assert not saved[:, 0].any() and not saved[:, -1].any() and not saved[:, :, 0].any() and not saved[:, :, -1].any()

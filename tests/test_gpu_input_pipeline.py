@@ -8,34 +8,36 @@ import pytest
 
 from oracle import np_ops as O
 from tests.test_gpu_full_model import CW, SHAPE, build, make_targets
+from _guard import guards  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("b,h,w,c,with_flip", [(3, 7, 13, 4, True), (2, 9, 16, 3, True), (1, 5, 5, 8, False), (4, 48, 64, 4, True)])
-def test_expand_inputs_bit_exact(ctx, rng, b, h, w, c, with_flip):
+def test_expand_inputs_bit_exact(ctx, guards, rng, b, h, w, c, with_flip):
     img = rng.integers(0, 256, (b, h, w, 3)).astype(np.uint8)
     idx = rng.integers(0, c + 2, (b, h, w)).astype(np.uint8)         # c, c+1: out of range -> all-zero one-hot rows
     flip = (np.arange(b) % 2 == 0).astype(np.uint8) if with_flip else None
     want_img, want_mask = O.expand_inputs(img, idx, flip, c)
-    d_img, d_mask = ctx.empty((b, h, w, 3)), ctx.empty((b, h, w, c))
-    d_flip = ctx.empty(b, np.uint8).upload(flip) if flip is not None else None
-    ctx.call("ssdseg_expand_inputs", ctx.empty(img.shape, np.uint8).upload(img), ctx.empty(idx.shape, np.uint8).upload(idx), d_flip, d_img, d_mask,
+    d_img, d_mask = guards.out((b, h, w, 3)), guards.out((b, h, w, c))
+    d_flip = guards.inp(flip, dtype=np.uint8) if flip is not None else None
+    ctx.call("ssdseg_expand_inputs", guards.inp(img, dtype=np.uint8), guards.inp(idx, dtype=np.uint8), d_flip, d_img, d_mask,
              b, h, w, c)
     np.testing.assert_array_equal(d_img.download(), want_img)
     np.testing.assert_array_equal(d_mask.download(), want_mask)
     # either half alone
-    d_img.zero_(); d_mask.zero_()
-    ctx.call("ssdseg_expand_inputs", ctx.empty(img.shape, np.uint8).upload(img), None, d_flip, d_img, None, b, h, w, c)
-    ctx.call("ssdseg_expand_inputs", None, ctx.empty(idx.shape, np.uint8).upload(idx), d_flip, None, d_mask, b, h, w, c)
+    guards.check()
+    guards.repoison(d_img); guards.repoison(d_mask)
+    ctx.call("ssdseg_expand_inputs", guards.inp(img, dtype=np.uint8), None, d_flip, d_img, None, b, h, w, c)
+    ctx.call("ssdseg_expand_inputs", None, guards.inp(idx, dtype=np.uint8), d_flip, None, d_mask, b, h, w, c)
     np.testing.assert_array_equal(d_img.download(), want_img)
     np.testing.assert_array_equal(d_mask.download(), want_mask)
 
 
-def test_expand_inputs_rejects_bad_arguments(ctx):
+def test_expand_inputs_rejects_bad_arguments(ctx, guards):
     from ssdseglib import _hip as H
-    buf = ctx.empty((1, 2, 2, 3))
-    u8 = ctx.empty((1, 2, 2, 3), np.uint8)
+    buf = guards.out((1, 2, 2, 3))
+    u8 = guards.out((1, 2, 2, 3), np.uint8)
     with pytest.raises(H.SsdsegError):
         ctx.call("ssdseg_expand_inputs", None, None, None, buf, None, 1, 2, 2, 4)       # nothing to expand
     with pytest.raises(H.SsdsegError):
@@ -44,7 +46,7 @@ def test_expand_inputs_rejects_bad_arguments(ctx):
         ctx.call("ssdseg_expand_inputs", u8, None, None, buf, None, 1, 2, 2, 9)         # more classes than the kernel's row
 
 
-def test_flip_gt_boxes_bit_exact(ctx, rng):
+def test_flip_gt_boxes_bit_exact(ctx, guards, rng):
     b, gmax, width = 5, 6, 640.0
     gt = np.zeros((b, gmax, 5), np.float32)
     cnt = rng.integers(0, gmax + 1, b).astype(np.int32)
@@ -58,8 +60,8 @@ def test_flip_gt_boxes_bit_exact(ctx, rng):
     for n in range(b):
         if flip[n]:
             want[n, :cnt[n]] = O.flip_gt_boxes(gt[n, :cnt[n]], width)
-    d = ctx.array(gt)
-    ctx.call("ssdseg_flip_gt_boxes", d, ctx.empty(b, np.int32).upload(cnt), ctx.empty(b, np.uint8).upload(flip), b, gmax, width)
+    d = guards.out(gt.shape).upload(gt)     # flipped in place
+    ctx.call("ssdseg_flip_gt_boxes", d, guards.inp(cnt, dtype=np.int32), guards.inp(flip, dtype=np.uint8), b, gmax, width)
     np.testing.assert_array_equal(d.download(), want)       # rows past the count and unflagged samples untouched
 
 
@@ -104,7 +106,7 @@ def _device_encoded(cb, targets):
     return dict(targets, **{'output-boxes': offsets})
 
 
-def test_compact_batch_fills_the_step_buffers_like_the_oracle(ctx, rng):
+def test_compact_batch_fills_the_step_buffers_like_the_oracle(ctx, guards, rng):
     """the engine's input / mask / label / offset buffers after a compact hand-over == the oracle's float tensors, bit for bit"""
     from ssdseglib import _engine as E
     E.set_default_context(ctx)
@@ -124,7 +126,7 @@ def test_compact_batch_fills_the_step_buffers_like_the_oracle(ctx, rng):
             np.testing.assert_array_equal(got.reshape(want[name].shape), want[name], err_msg=name)
 
 
-def test_fit_on_compact_batches_equals_fit_on_float_tensors(ctx, rng, monkeypatch):
+def test_fit_on_compact_batches_equals_fit_on_float_tensors(ctx, guards, rng, monkeypatch):
     """model.fit over compact batches (uploads overlapped with the running step, and synchronous) gives the history of the
     same fit over the expanded float32 tensors -- identical device kernels on identical inputs, so identical bits; a smaller
     last batch goes through another engine"""

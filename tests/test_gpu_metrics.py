@@ -8,6 +8,7 @@ import pytest
 from oracle import np_ops as O
 from oracle.np_model import NpModel
 from tests.test_gpu_full_model import CW, STDS, build, make_targets
+from _guard import guards  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -15,7 +16,7 @@ LW = (0.0, 1 / 3, 1 / 3, 1 / 3)    # NB03#cell14
 
 
 @pytest.mark.parametrize("n,h,w", [(2, 12, 16), (3, 60, 80), (1, 1, 1)])
-def test_mask_iou_from_probabilities(ctx, rng, n, h, w):
+def test_mask_iou_from_probabilities(ctx, guards, rng, n, h, w):
     import ssdseglib
     from ssdseglib import _engine as E
     E.set_default_context(ctx)
@@ -28,18 +29,18 @@ def test_mask_iou_from_probabilities(ctx, rng, n, h, w):
 
 
 @pytest.mark.parametrize("n,h,w,f", [(2, 6, 8, 4), (1, 30, 40, 4), (2, 5, 3, 2)])
-def test_mask_iou_from_logits(ctx, rng, n, h, w, f):
+def test_mask_iou_from_logits(ctx, guards, rng, n, h, w, f):
     """the training path: soft Jaccard against softmax(bilinear x f (logits)) recomputed per pixel, nothing stored"""
     logits = rng.normal(0, 2, (n, h, w, 4)).astype(np.float32)
     t = np.eye(4, dtype=np.float32)[rng.integers(0, 4, (n, h * f, w * f))]
     p_ref = O.softmax(O.bilinear_fwd(logits.astype(np.float64), f, f))
-    out = ctx.empty(n)
-    ctx.call("ssdseg_metric_mask_iou", ctx.array(logits), n, h, w, 4, f, f, 1, ctx.array(t), (C.c_float * 4)(*CW), out)
+    out = guards.out(n)
+    ctx.call("ssdseg_metric_mask_iou", guards.inp(logits), n, h, w, 4, f, f, 1, guards.inp(t), (C.c_float * 4)(*CW), out)
     assert np.abs(out.download() - O.metric_mask_iou(t, p_ref, CW)).max() < 1e-5
 
 
 @pytest.mark.parametrize("b,a", [(3, 500), (2, 9600), (1, 7)])
-def test_label_accuracy(ctx, rng, b, a):
+def test_label_accuracy(ctx, guards, rng, b, a):
     import ssdseglib
     from ssdseglib import _engine as E
     E.set_default_context(ctx)
@@ -51,7 +52,7 @@ def test_label_accuracy(ctx, rng, b, a):
 
 
 @pytest.mark.parametrize("b,a,pos", [(3, 600, 0.05), (2, 9600, 0.01), (2, 50, 0.0)])
-def test_box_iou(ctx, rng, b, a, pos):
+def test_box_iou(ctx, guards, rng, b, a, pos):
     import ssdseglib
     from ssdseglib import _engine as E
     E.set_default_context(ctx)
@@ -70,7 +71,7 @@ def test_box_iou(ctx, rng, b, a, pos):
         m(t[:, :-1], p[:, :-1])
 
 
-def test_metrics_inside_train_step_and_fit(ctx, rng):
+def test_metrics_inside_train_step_and_fit(ctx, guards, rng):
     """compile(metrics=...) as NB03#cell14: history keys and values == the oracle's metrics of the same forward pass"""
     import ssdseglib
     from ssdseglib import _engine as E

@@ -10,6 +10,7 @@ import pytest
 
 from tests.test_gpu_input_pipeline import _compact_batches, _compile, _device_encoded
 from tests.test_gpu_full_model import build
+from _guard import guards  # noqa: F401  (fixture)
 
 LOW = (-0.05, 0.95, 0.90, -0.10)        # the low end of every reference range (datacoder.py:452-461)
 HIGH = (0.05, 1.05, 1.10, 0.10)         # the high end
@@ -96,11 +97,11 @@ def _host(img, flip, draws):
     return want, q.astype(np.float64).mean(axis=(1, 2)), q.mean(axis=(1, 2))
 
 
-def _device(ctx, img, flip, draws):
+def _device(ctx, guards, img, flip, draws):
     b, h, w, _ = img.shape
-    means, out = ctx.empty((b, 3)), ctx.empty((b, h, w, 3))
-    d_flip = ctx.empty(b, np.uint8).upload(flip) if flip is not None else None
-    ctx.call("ssdseg_rgb_augment", ctx.empty(img.shape, np.uint8).upload(img), d_flip, (C.c_float * 4)(*draws), means, out, b, h, w)
+    means, out = guards.out((b, 3)), guards.out((b, h, w, 3))
+    d_flip = guards.inp(flip, dtype=np.uint8) if flip is not None else None
+    ctx.call("ssdseg_rgb_augment", guards.inp(img, dtype=np.uint8), d_flip, (C.c_float * 4)(*draws), means, out, b, h, w)
     return out.download(), means.download()
 
 
@@ -110,7 +111,7 @@ CASES = [(s, d) for s in [(3, 7, 13), (1, 5, 5), (2, 9, 16), (4, 48, 64)] for d 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape,draws", CASES)
-def test_rgb_augment_matches_the_host_spec(ctx, rng, shape, draws):
+def test_rgb_augment_matches_the_host_spec(ctx, guards, rng, shape, draws):
     draws = _f32(draws)
     img = _pixels(rng, *shape)
     want, m64, m32 = _host(img, None, draws)
@@ -119,7 +120,8 @@ def test_rgb_augment_matches_the_host_spec(ctx, rng, shape, draws):
     tol = ATOL + abs(1.0 - draws[2]) * float(np.abs(m32 - m64).max())
     flip = (np.arange(shape[0]) % 2 == 0).astype(np.uint8)
     for f in (None, flip):
-        got, means = _device(ctx, img, f, draws)
+        got, means = _device(ctx, guards, img, f, draws)
+        guards.check()
         np.testing.assert_allclose(means, m64, rtol=1e-5)
         w = want if f is None else np.where(f[:, None, None, None] != 0, want[:, :, ::-1], want)
         err = float(np.abs(got - w).max())
@@ -128,18 +130,18 @@ def test_rgb_augment_matches_the_host_spec(ctx, rng, shape, draws):
 
 
 @pytest.mark.gpu
-def test_rgb_augment_is_deterministic(ctx, rng):
+def test_rgb_augment_is_deterministic(ctx, guards, rng):
     img = _pixels(rng, 32, 480, 640)
     flip = rng.integers(0, 2, 32).astype(np.uint8)
-    a, ma = _device(ctx, img, flip, _f32(HIGH))
-    b, mb = _device(ctx, img, flip, _f32(HIGH))
+    a, ma = _device(ctx, guards, img, flip, _f32(HIGH))
+    b, mb = _device(ctx, guards, img, flip, _f32(HIGH))
     assert a.tobytes() == b.tobytes() and ma.tobytes() == mb.tobytes()
 
 
 @pytest.mark.gpu
-def test_rgb_augment_rejects_bad_arguments(ctx):
+def test_rgb_augment_rejects_bad_arguments(ctx, guards):
     from ssdseglib import _hip as H
-    u8, means, out = ctx.empty((1, 2, 4, 3), np.uint8), ctx.empty((1, 3)), ctx.empty((1, 2, 4, 3))
+    u8, means, out = guards.out((1, 2, 4, 3), np.uint8), guards.out((1, 3)), guards.out((1, 2, 4, 3))
     draws = (C.c_float * 4)(*IDENTITY)
     with pytest.raises(H.SsdsegError):
         ctx.call("ssdseg_rgb_augment", None, None, draws, means, out, 1, 2, 4)
@@ -162,7 +164,7 @@ def _target_buffers(eng):
 
 
 @pytest.mark.gpu
-def test_loader_augments_only_the_image(ctx, rng):
+def test_loader_augments_only_the_image(ctx, guards, rng):
     from ssdseglib import _engine as E
     E.set_default_context(ctx)
     (cb, _, _), = _compact_batches(rng, (3,))
@@ -183,23 +185,23 @@ def test_loader_augments_only_the_image(ctx, rng):
         assert buf.tobytes() == plain[name].tobytes(), name
 
 
-def _augmented_data(ctx, rng, sizes, draw_sets):
+def _augmented_data(ctx, guards, rng, sizes, draw_sets):
     """(augmented compact batch, the same batch as float tensors: the ssdseg_rgb_augment image downloaded, device-encoded targets)"""
     out = []
     for (cb, _, t), draws in zip(_compact_batches(rng, sizes), draw_sets):
         aug = _augmented(cb, draws)
-        img, _ = _device(ctx, cb.images, cb.flip, aug.rgb_draws)
+        img, _ = _device(ctx, guards, cb.images, cb.flip, aug.rgb_draws)
         out.append((aug, img, _device_encoded(cb, t)))
     return out
 
 
 @pytest.mark.gpu
-def test_fit_on_augmented_compact_batches_equals_fit_on_float_tensors(ctx, rng, monkeypatch):
+def test_fit_on_augmented_compact_batches_equals_fit_on_float_tensors(ctx, guards, rng, monkeypatch):
     """fit over augmented compact batches -- uploads overlapped with the running step, and synchronous -- gives the history of
     the same fit over the augmented float32 tensors, bit for bit; a smaller last batch goes through another engine"""
     from ssdseglib import _engine as E
     E.set_default_context(ctx)
-    data = _augmented_data(ctx, rng, (3, 3, 3, 2), (LOW, HIGH, CLAMP, (0.02, 0.97, 1.04, -0.06)))
+    data = _augmented_data(ctx, guards, rng, (3, 3, 3, 2), (LOW, HIGH, CLAMP, (0.02, 0.97, 1.04, -0.06)))
     hist = {}
     for mode in ("compact-overlap", "compact-sync", "float"):
         monkeypatch.setenv("SSDSEG_FIT_OVERLAP", "0" if mode == "compact-sync" else "1")
@@ -214,12 +216,12 @@ def test_fit_on_augmented_compact_batches_equals_fit_on_float_tensors(ctx, rng, 
 
 
 @pytest.mark.gpu
-def test_fit_validates_on_compact_batches(ctx, rng):
+def test_fit_validates_on_compact_batches(ctx, guards, rng):
     """validation_data as compact batches (augmented or not) gives the val_* history of the same batches as float tensors"""
     from ssdseglib import _engine as E
     E.set_default_context(ctx)
-    train = [cb for cb, _, _ in _augmented_data(ctx, rng, (3, 3), (LOW, HIGH))]
-    val = _augmented_data(ctx, rng, (3, 2), (HIGH, IDENTITY))
+    train = [cb for cb, _, _ in _augmented_data(ctx, guards, rng, (3, 3), (LOW, HIGH))]
+    val = _augmented_data(ctx, guards, rng, (3, 2), (HIGH, IDENTITY))
     (plain_cb, plain_img, plain_t), = [(cb, img, _device_encoded(cb, t)) for cb, img, t in _compact_batches(rng, (3,))]
     hist = {}
     for mode in ("compact", "float"):

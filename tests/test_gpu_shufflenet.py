@@ -6,8 +6,15 @@ import pytest
 
 from oracle.np_model import NpModel
 from tests.test_gpu_backbone import device_relu_masks, rel
+from _guard import poisoned_ctx  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _ctx_poison(poisoned_ctx):
+    """every activation, statistics table and workspace region of the engine starts as NaN (tests/_guard.py)"""
+    return poisoned_ctx
 
 TAPS = ['backbone-stage3-block7-reshape-post-channels-shuffle', 'backbone-stage4-block3-reshape-post-channels-shuffle',
         'backbone-stage2-block3-reshape-post-channels-shuffle']

@@ -19,8 +19,15 @@ from oracle import np_ops as O
 from oracle.np_model import NpModel
 from tests.test_gpu_backbone import device_relu_masks, rel
 from tests.test_gpu_full_model import CW, SHAPE, build, make_targets
+from _guard import poisoned_ctx  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _ctx_poison(poisoned_ctx):
+    """every activation, statistics table and workspace region of the engine starts as NaN (tests/_guard.py)"""
+    return poisoned_ctx
 
 U = 2.0 ** -24          # unit roundoff of fp32
 LR = 1e-2               # large enough that one step moves every gradient well past the 1e-3 bound (sensitivity control)
