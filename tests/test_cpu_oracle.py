@@ -258,3 +258,50 @@ def test_config0_single_480x640_forward_through_the_oracle():
     ref = NpModel(inference, dtype=np.float32)
     seg, det = ref.forward(x, training=False)
     assert seg.shape == (1, 480, 640, 4) and det.shape == (1, 10, 6)
+
+
+def test_det_edge_case_is_self_consistent_between_float32_and_float64():
+    """The hand-made clip / threshold inputs of tests/test_gpu_head_ops.py::test_det_loss_clip_and_threshold_edges, oracle against
+    oracle: with float32 constants (the device's: lo = float32(1e-7), hi = 1 - 2^-23, the reference's tf.clip_by_value on float32
+    tensors) and with float64 ones (1e-7, 1 - 1e-7) every input lies on the same side of both boundaries and the hard-negative
+    selection is the same set, so the GPU test compares against an unambiguous answer; the mining-run helpers of
+    test_det_loss_saturated_ties place k where they say."""
+    from tests.test_gpu_head_ops import (BOX_ERRORS, CLIP_EDGES, HI32, LO32, det_edge_expectations, make_det_edge_case, mining_run,
+                                         saturated_case, tie_run_case)
+    assert float(LO32) > 1e-7 > float(np.nextafter(LO32, np.float32(0)))
+    assert float(HI32) == 1 - 2.0 ** -23 and float(HI32) < 1 - 1e-7 < float(np.nextafter(HI32, np.float32(1)))
+    rng = np.random.default_rng(1993)
+    y, p, yb, pb = make_det_edge_case(rng)
+    assert p.dtype == np.float32 and set(CLIP_EDGES.tolist()) <= set(p[y == 1].tolist())
+    _, inside32 = O._clipped_log(p)
+    _, inside64 = O._clipped_log(p.astype(np.float64))
+    want32, n_low, n_high = det_edge_expectations(y, p)
+    assert np.array_equal(inside32.astype(bool), want32) and np.array_equal(inside64.astype(bool), want32)
+    assert 0 < (~want32).sum() < want32.size // 8
+    l32, d32, keep32 = O.confidence_loss(y, p)
+    l64, d64, keep64 = O.confidence_loss(y.astype(np.float64), p.astype(np.float64))
+    assert np.array_equal(keep32, keep64)
+    k = int(keep32.sum())
+    n_ord = int((y[..., 0] == 1).sum()) - n_low - n_high
+    assert n_low >= 5 and n_high >= 5 and n_low < k < n_ord, (n_low, n_high, k, n_ord)     # edge anchors off the selection border
+    assert np.allclose(l32, l64, rtol=1e-5) and np.allclose(d32, d64, rtol=1e-5, atol=1e-12)
+    # smooth-L1: the hand-made errors are exact, and both precisions take the same branch at every element
+    e32, e64 = yb - pb, yb.astype(np.float64) - pb.astype(np.float64)
+    assert np.array_equal(e32[0, :len(BOX_ERRORS)].astype(np.float64), e64[0, :len(BOX_ERRORS)])
+    assert np.array_equal(np.abs(e32) < 1, np.abs(e64) < 1) and np.array_equal(np.sign(e32), np.sign(e64))
+    hits = {float(np.float32(t) - np.float32(q)) for t, q in BOX_ERRORS}
+    assert hits == {0.0, 1.0, -1.0, 1 - 2.0 ** -24, -(1 - 2.0 ** -24), 1 + 2.0 ** -23, -(1 + 2.0 ** -23)} and hits <= set(e32[..., 0].ravel().tolist())
+    q32, g32 = O.localization_loss(yb, pb)
+    q64, g64 = O.localization_loss(yb.astype(np.float64), pb.astype(np.float64))
+    assert np.allclose(q32, q64, rtol=1e-6) and np.allclose(g32, g64, rtol=1e-6, atol=0)
+    # tie runs
+    for where in ("first", "last"):
+        yt, pt, G, R, P = tie_run_case(rng, 3, 9600, where)
+        k, kth, rank, run = mining_run(yt, pt)
+        assert (k, run, rank) == (3 * P, R, 1 if where == "first" else R)
+        _, _, keep = O.confidence_loss(yt, pt)
+        _, _, keepd = O.confidence_loss(yt.astype(np.float64), pt.astype(np.float64))
+        assert keep.sum() == k and np.array_equal(keep, keepd)
+    ys, ps = saturated_case(rng, 3, 9600, 0.01)
+    k, kth, rank, run = mining_run(ys, ps)
+    assert run > 300 and 1 <= rank <= run

@@ -583,3 +583,224 @@ def test_conv3x3_saved_input_pair_equals_plain_entry_points(ctx, guards, rng, mo
     assert ctx.lib.ssdseg_conv3x3_saved_floats(1, 5, 5, 24, 8, C.byref(need)) == 0 and need.value == 0
     with pytest.raises(H.SsdsegError):
         ctx.call("ssdseg_conv3x3_fwd_saved", H.view(dx_), 24, dw_, y1, 1, 5, 5, 24, 8, None, xs)
+
+
+# ------------------------------------------------------------------------------------ detection loss: call forms and edges
+F32 = np.float32
+LO32 = F32(1e-7)                       # the device's KEPS
+HI32 = F32(1.0) - F32(1e-7)            # the device's 1.f - KEPS, formed in float32: 1 - 2^-23
+CLIP_EDGES = np.array([0.0, 1.0, 5e-8, LO32, np.nextafter(LO32, F32(0)), np.nextafter(LO32, F32(1)),
+                       1.0 - 5e-8, HI32, np.nextafter(HI32, F32(0)), np.nextafter(HI32, F32(1))], np.float32)
+BOX_ERRORS = [(3.0, 3.0), (2.0, 1.0), (1.0, 2.0),                                   # e = 0, +1, -1
+              (float(np.nextafter(F32(1), F32(0))), 0.0), (2.0 ** -24, 1.0),        # e = +-(1 - 2^-24): the quadratic side
+              (float(np.nextafter(F32(1), F32(2))), 0.0), (-2.0 ** -23, 1.0)]       # e = +-(1 + 2^-23): the linear side
+
+
+def make_det_edge_case(rng, b=2, a=640):
+    """Detection-loss inputs built by hand (float32), not from a softmax of bounded logits.
+
+    Probabilities: every value of CLIP_EDGES as the TRUE-class probability of a positive anchor (each class 1..3) and of a
+    background anchor, plus exact one-hot rows read with the right and with a wrong label; the other anchors are ordinary
+    background (true-class probability in [0.05, 0.95]).  Which side of a clip boundary an input lies on is the same for the
+    float32 constants (the device, the float32 oracle: lo = float32(1e-7) > 1e-7, hi = 1 - 2^-23 < 1 - 1e-7) and the float64 ones,
+    because no float32 number lies in [1e-7, lo) or in (hi, 1 - 1e-7]: lo's float32 predecessor is below 1e-7 and hi's successor,
+    1 - 2^-24, is above 1 - 1e-7.  The clipped VALUE differs (log(hi) is 1.19e-7 against 1.0e-7): that moves mining keys of
+    1e-7, so the case keeps every edge background anchor off the selection border: those at the low edge have the largest keys
+    of the batch (16.1 against < 3 for the ordinary ones) and k exceeds their number, those at the high edge the smallest and
+    k stays below the number of ordinary ones.  Boxes: errors of exactly 0, +-1, +-(1 - 2^-24) and +-(1 + 2^-23) (BOX_ERRORS;
+    every subtraction is exact in float32), and one image-1 anchor row so that image 1 is not empty either."""
+    n_e = CLIP_EDGES.size
+    p = np.zeros((b, a, 4), np.float32)
+    cls = np.zeros((b, a), np.int64)
+    # ordinary background anchors everywhere first
+    pt = rng.uniform(0.05, 0.95, (b, a)).astype(np.float32)
+    p[..., 0] = pt
+    p[..., 1:] = ((1 - pt) / 3)[..., None]
+    i = 0
+    for c in (1, 2, 3):                                   # positives whose true-class probability is an edge value
+        for v in CLIP_EDGES:
+            row = np.full(4, (1 - v) / 3, np.float32)
+            row[c] = v
+            p[0, i], cls[0, i] = row, c
+            i += 1
+    for v in CLIP_EDGES:                                  # background anchors at the edges (image 1)
+        row = np.full(4, (1 - v) / 3, np.float32)
+        row[0] = v
+        p[1, i], cls[1, i] = row, 0
+        i += 1
+    for c_true, c_hot in ((1, 1), (2, 1), (0, 0), (0, 3), (3, 0)):   # exact one-hot rows, right and wrong label
+        p[0, i], cls[0, i] = np.eye(4, dtype=np.float32)[c_hot], c_true
+        i += 1
+    assert i < a // 4
+    y = np.eye(4, dtype=np.float32)[cls]
+    yb = np.zeros((b, a, 4), np.float32)
+    pb = rng.uniform(0, 6, (b, a, 4)).astype(np.float32)
+    pos = np.argwhere(cls > 0)
+    yb[cls > 0] = rng.normal(0, 2, (len(pos), 4)).astype(np.float32)
+    for j, (t, q) in enumerate(BOX_ERRORS):               # the first positives carry the exact box errors, one per coordinate slot
+        bi, ai = pos[j]
+        yb[bi, ai] = (t, 1.0, t, 1.0)
+        pb[bi, ai] = (q, 0.25, q, 3.5)
+    yb[1, a - 1] = (0.5, -0.5, 0.25, 2.0)                 # a box target on an anchor of image 1 (localization only: its label stays background)
+    return y, p, yb, pb
+
+
+def det_edge_expectations(y, p):
+    """(inside pattern under float32 constants, number of edge background anchors at the low / high edge)"""
+    inside32 = (p >= LO32) & (p <= HI32)
+    bg_true = p[..., 0][y[..., 0] == 1]
+    return inside32, int((bg_true <= np.nextafter(LO32, F32(1))).sum()), int((bg_true >= np.nextafter(HI32, F32(0))).sum())
+
+
+def test_det_loss_clip_and_threshold_edges(ctx, guards, rng):
+    """clipf / insidef at exact 0, 1 and both neighbours of each clip constant, smooth-L1 at |e| = 1 exactly and one ulp either
+    side, sign(0): loss, both gradients and the keep mask against the oracle on the same float32 inputs (tests/test_cpu_oracle.py
+    shows the float32 and float64 oracles agree on `inside` and on the mask for these inputs); bounds of test_det_loss."""
+    b, a = 2, 640
+    y, p, yb, pb = make_det_edge_case(rng, b, a)
+    conf_ref, dp_ref, keep_ref = O.confidence_loss(y, p)
+    loc_ref, dloc_ref = O.localization_loss(yb, pb)
+    scale = 1.0 / b
+    dlogits_ref = O.softmax_bwd(p.astype(np.float64), dp_ref.astype(np.float64)) * scale
+    conf, loc = guards.out(b), guards.out(b)
+    dlog, dbox = guards.out((b, a, 4)), guards.out((b, a, 4))
+    keep = guards.out(b * a, np.uint8)
+    ctx.call("ssdseg_det_loss", guards.inp(y), guards.inp(p), guards.inp(yb), guards.inp(pb), b, a, 4, scale, conf, loc, dlog, dbox, keep)
+    assert np.array_equal(keep.download(), keep_ref)
+    got = dlog.download()
+    assert rel_err(got, dlogits_ref) < 2e-5
+    # the inside = 0 form exactly: a positive whose true-class probability is outside the clip range has a zero gradient row
+    inside32, _, _ = det_edge_expectations(y, p)
+    dead = (y[..., 1:].sum(-1) == 1) & ~(inside32 & (y == 1)).any(-1)
+    assert dead.sum() >= 12 and not got[dead].any()
+    assert rel_err(conf.download(), conf_ref) < 1e-5
+    assert rel_err(loc.download(), loc_ref) < 1e-5
+    assert np.abs(dbox.download() - dloc_ref * scale).max() < 1e-6
+
+
+def test_det_loss_optional_outputs(ctx, guards, rng):
+    """every NULL-subset of the outputs the product uses (training: all but the mask; evaluation: losses only;
+    losses.confidence_loss / localization_loss: one loss): what is present is bit-identical to the full call"""
+    b, a = 3, 2400
+    y, p, yb, pb = make_det_case(rng, b, a, 0.02)
+    ins = [guards.inp(v) for v in (y, p, yb, pb)]
+    names = ("conf", "loc", "dlog", "dbox", "keep")
+
+    def call(present):
+        shapes = dict(conf=(b,), loc=(b,), dlog=(b, a, 4), dbox=(b, a, 4), keep=(b * a,))
+        outs = {k: guards.out(shapes[k], np.uint8 if k == "keep" else np.float32) for k in present}
+        ctx.call("ssdseg_det_loss", *ins, b, a, 4, 1.0 / b, *[outs.get(k) for k in names])
+        ctx.sync()
+        guards.check()
+        for k in present:
+            if k != "keep":                         # (a uint8 element may equal the pattern byte by chance)
+                assert guards.unwritten(outs[k]).size == 0, k
+        return {k: outs[k].download() for k in present}
+
+    full = call(names)
+    assert np.isfinite(full["dlog"]).all() and np.abs(full["dlog"]).max() > 0 and full["keep"].sum() > 0
+    for present in (("conf", "loc", "keep"), ("conf", "loc", "dlog", "dbox"), ("conf",), ("loc",), ("dlog", "dbox", "keep")):
+        part = call(present)
+        for k in present:
+            assert np.array_equal(part[k].view(np.uint8), full[k].view(np.uint8)), (present, k)
+
+
+def saturated_case(rng, b, a, pos_frac):
+    """logits drawn from {0, 1.5, 6} per class (the heads pass ReLU6, quirk Q3: trained logits pile up at 0 and 6)"""
+    logits = rng.choice(np.array([0.0, 1.5, 6.0]), (b, a, 4))
+    p = O.softmax(logits).astype(np.float32)
+    cls = np.where(rng.uniform(size=(b, a)) < pos_frac, rng.integers(1, 4, (b, a)), 0)
+    return np.eye(4, dtype=np.float32)[cls], p
+
+
+def tie_run_case(rng, b, a, where):
+    """3 * #positives lands exactly on the FIRST / LAST element of a run of equal mining keys: G background anchors with the
+    batch's largest key (logits 0 | 6 6 6), R with the second largest (1.5 | 6 6 6), the rest with a small one (6 | 0 0 0),
+    P positives, all scattered over the images; first: 3 P = G + 1, last: 3 P = G + R"""
+    n, P = b * a, 96
+    G, R = (3 * P - 1, 2000) if where == "first" else (3 * P - 200, 200)
+    rows = O.softmax(np.array([[0, 6, 6, 6], [1.5, 6, 6, 6], [6, 0, 0, 0], [0, 6, 1.5, 0]], np.float64)).astype(np.float32)
+    kind = np.full(n, 2)
+    kind[:G], kind[G:G + R], kind[G + R:G + R + P] = 0, 1, 3
+    kind = rng.permutation(kind)
+    p = rows[kind].reshape(b, a, 4)
+    cls = np.where(kind == 3, 1, 0).reshape(b, a)
+    return np.eye(4, dtype=np.float32)[cls], p, G, R, P
+
+
+def mining_run(y, p):
+    """(k, value of the k-th largest background key, rank of the k-th inside its run of equal keys (1-based), run length)"""
+    logp, _ = O._clipped_log(p)
+    bg = (-(y * logp).sum(-1) * y[..., 0]).reshape(-1)
+    k = min(3 * int((y[..., 0] == 0).sum()), int((y[..., 0] == 1).sum()))
+    kth = np.sort(bg)[::-1][k - 1]
+    return k, kth, k - int((bg > kth).sum()), int((bg == kth).sum())
+
+
+@pytest.mark.parametrize("case", ["random", "first", "last"])
+def test_det_loss_saturated_ties(ctx, guards, rng, case):
+    """whole runs of anchors with the same mining key, across images: the kept set is the oracle's bit for bit (lowest flat
+    index first, across image borders), also when k is the first or the last element of a run"""
+    b, a = 3, 9600
+    if case == "random":
+        y, p = saturated_case(rng, b, a, 0.01)
+        k, kth, rank, run = mining_run(y, p)
+        assert run > 300 and 1 <= rank <= run, (k, kth, rank, run)
+    else:
+        y, p, G, R, P = tie_run_case(rng, b, a, case)
+        k, kth, rank, run = mining_run(y, p)
+        assert k == 3 * P and run == R and rank == (1 if case == "first" else R), (k, kth, rank, run)
+    cut = np.flatnonzero((y[..., 0] == 1).reshape(-1) & (O._clipped_log(p)[0][..., 0].reshape(-1) == -kth))
+    assert cut[0] < a and cut[-1] >= (b - 1) * a, "the tie run should span the image borders"
+    zeros = np.zeros((b, a, 4), np.float32)
+    conf_ref, _, keep_ref = O.confidence_loss(y, p)
+    assert keep_ref.sum() == k
+    conf, keep = guards.out(b), guards.out(b * a, np.uint8)
+    dz = guards.inp(zeros)
+    ctx.call("ssdseg_det_loss", guards.inp(y), guards.inp(p), dz, dz, b, a, 4, 1.0, conf, None, None, None, keep)
+    got = keep.download()
+    assert np.array_equal(got, keep_ref), f"{int((got != keep_ref).sum())} hard-negative decisions differ from the oracle"
+    assert rel_err(conf.download(), conf_ref) < 1e-5
+
+
+def test_mask_head_clip_edge(ctx, guards, rng):
+    """the mask head's clipped log and its zero gradient outside the clip range: a logit gap of 20, flat over a region so that the
+    bilinear keeps it, puts the true-class probability below 1e-7 (true class 1: 2e-9) or at 1 (true class 0: rounds to 1.0f).
+    Where a pixel's true-class probability is outside the range the loss gradient is the `inside = 0` form: exactly zero, so
+    low-resolution logits whose whole bilinear footprint lies in the region get an exactly zero gradient.  Everywhere else the
+    true class is chosen so that its probability is at least 1 % away from either clip constant (asserted on the oracle's
+    probabilities), so float32 and float64 agree on `inside` by construction."""
+    n, h, w, c, f = 2, 12, 16, 4, 4
+    logits = rng.normal(0, 2, (n, h, w, c)).astype(np.float32)
+    logits[:, 1:10, 2:13] = 0.0                           # a ring of equal logits: the transition's gaps are 20 q, q a product of eighths
+    logits[:, 2:9, 3:12] = (20.0, 0.0, 0.0, 0.0)
+    up = O.bilinear_fwd(logits.astype(np.float64), f, f)
+    p_ref = O.softmax(up)
+    cls = rng.integers(0, c, (n, h * f, w * f))
+    zone = np.zeros((n, h * f, w * f), bool)
+    zone[:, 1 * f:10 * f, 2 * f:13 * f] = True            # the region and the transition around it
+    cls[zone] = 1
+    sat = p_ref[..., 0] > 1 - 1e-8                        # rounds to 1.0f whatever the last bits of the device's softmax
+    cls[sat & (np.arange(w * f) % 2 == 0)] = 0            # half of the saturated pixels: true class 0 (p = 1), the others class 1 (p = 2e-9)
+    y = np.eye(c, dtype=np.float32)[cls]
+    pt = (p_ref * y).sum(-1)
+    safe = (pt > 1 - 1e-8) | ((np.abs(pt - 1e-7) > 1e-9) & (pt < 1 - 2e-7))
+    assert safe.all(), "a true-class probability too close to a clip constant: inside would depend on float32 rounding"
+    outside = (pt < 1e-7) | (pt > 1 - 1e-7)
+    assert (outside & (cls == 1)).sum() > 500 and (outside & (cls == 0)).sum() > 500
+    cw = np.array([0.05, 0.575, 0.135, 0.24], np.float32)
+    loss_ref, dp = O.cross_entropy_loss(y.astype(np.float64), p_ref, cw.astype(np.float64))
+    assert not dp[outside].any()
+    dlogits_ref = O.bilinear_bwd(O.softmax_bwd(p_ref, dp * 0.5), f, f)
+    cwh = (C.c_float * 4)(*cw)
+    dl, dy = guards.inp(logits), guards.inp(y)
+    prob, loss = guards.out(y.shape), guards.out(n)
+    ctx.call("ssdseg_mask_head_fwd", dl, n, h, w, c, f, f, dy, cwh, prob, loss)
+    assert np.abs(prob.download() - p_ref).max() < 2e-6
+    assert rel_err(loss.download(), loss_ref) < 1e-5
+    g = guards.out(logits.shape)
+    ctx.call("ssdseg_mask_head_bwd", dl, n, h, w, c, f, f, dy, cwh, 0.5, g)
+    got = g.download()
+    assert rel_err(got, dlogits_ref) < 2e-5
+    dead = ~dlogits_ref.any(-1)
+    assert dead[:, 3:8, 4:11].all() and not got[dead].any()
