@@ -118,7 +118,6 @@ struct RowGeom {
     int c, cv;
 };
 
-__device__ __forceinline__ void add4(float4& a, float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
 
 __device__ __forceinline__ float4 reduce_over_y(float4 v, float4* red) {
     __syncthreads();

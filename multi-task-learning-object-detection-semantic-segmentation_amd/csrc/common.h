@@ -88,6 +88,11 @@ int ssdseg_workspace(ssdseg_ctx* ctx, size_t bytes, void** out);
 // storage for the partial slabs / rows a later ssdseg_colsum reads: the stream's workspace, or -- while column sums are deferred
 // (ssdseg_colsum_defer) -- a persistent arena whose regions live until the flush (bn.hip)
 int ssdseg_partials(ssdseg_ctx* ctx, size_t bytes, void** out);
+// bn.hip: (dgamma, dbeta, k1, k0) from nparts partial rows of (sum mask*g, sum mask*g*xhat)
+int ssdseg_bn_bwd_finalize_launch(ssdseg_ctx* ctx, const float* part, int nparts, int c, double count, const float* scale,
+                                  const float* mean, const float* invstd, float* dgamma, float* dbeta, float* k1, float* k0);
+// bn.hip: out[i] = sum over the nparts rows of part[.][len], fixed order
+int ssdseg_colsum(ssdseg_ctx* ctx, const float* part, int nparts, long long len, float* out);
 // launches the pending column sums of a deferred backward pass as ONE kernel on the ctx stream (called by ssdseg_join once the
 // side stream has been joined); no-op when nothing is pending
 int ssdseg_colsum_flush(ssdseg_ctx* ctx);
@@ -133,6 +138,10 @@ static inline void same_pad(int in, int k, int s, int d, int* out, int* before) 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
 // Keras ReLU(max_value) (App. B.4) as a clamp to [lo, hi] -- branch-free on the (wave-uniform) activation code:
 //   NONE [-inf, +inf] | RELU [0, +inf] | RELU6 [0, 6] | ZERO (max_value = 0.0, quirk Q1) [0, 0]
 __device__ __forceinline__ float act_lo(int act) { return act == SSDSEG_ACT_NONE ? -INFINITY : 0.f; }
@@ -144,6 +153,7 @@ __device__ __forceinline__ float act_mask(float z, int act) { return (z > act_lo
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
+__device__ __forceinline__ void add4(float4& acc, float4 a) { acc.x += a.x; acc.y += a.y; acc.z += a.z; acc.w += a.w; }
 
 // a = act(scale*x + shift) on a 4-channel vector; has_affine == false -> act(x)
 __device__ __forceinline__ float4 view_apply4(float4 x, float4 s, float4 t, bool has_affine, int act) {
@@ -198,6 +208,28 @@ __device__ __forceinline__ BlockPos xcd_block_pos() {
     p.y = (int)(logical / gridDim.x);
     p.x = (int)(logical - (unsigned)p.y * gridDim.x);
     return p;
+}
+
+// global -> LDS copy of 16 bytes per lane (buffer_load_dwordx4 ... lds), written as inline asm ON PURPOSE: through the builtin the
+// compiler's wait-count pass orders every later ds_read behind the pending LDS write (it cannot tell the two buffers apart) and
+// put `s_waitcnt vmcnt(<loads issued after the DMA>)` in front of the first fragment read of every step -- i.e. the prefetch was
+// waited for right after it was issued.  An asm statement is invisible to that pass; completion is OUR job: the DMA is older
+// than the step's register loads (the counter is in-order), commit() ends with an explicit vmcnt(0), and the barrier follows.
+// lds_byte_addr: wave-uniform LDS address of lane 0's 16 bytes (lane l lands at +16*l); M0 is saved and restored in the statement.
+typedef int pwt_i32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ pwt_i32x4 pwt_make_rsrc(const void* base, unsigned bytes) {
+    const unsigned long long a = (unsigned long long)base;
+    pwt_i32x4 r;
+    r.x = (int)(unsigned)(a & 0xffffffffull);
+    r.y = (int)(unsigned)((a >> 32) & 0xffffull);     // stride 0
+    r.z = (int)bytes;                                    // num_records (bytes): offsets beyond it read zeros
+    r.w = 0x00020000;
+    return r;
+}
+__device__ __forceinline__ void lds_dma16(pwt_i32x4 rsrc, unsigned lds_byte_addr, unsigned voffset, int soffset) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(voffset), "s"(rsrc), "s"(soffset) : "memory");
 }
 
 __device__ __forceinline__ float wave_sum(float v) {

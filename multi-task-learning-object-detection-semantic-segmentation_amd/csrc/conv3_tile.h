@@ -1,5 +1,5 @@
 // Dense 3x3 stride-1 SAME convolution (DeepLabV3+ decoder, reference blocks.py:117) forward and input gradient as a
-// HALO-TILE kernel -- included by gemm.hip inside its anonymous namespace.
+// HALO-TILE kernel -- included by conv3.hip inside its anonymous namespace.
 //
 // The implicit-GEMM form (gemm_rowA_kernel<.., LD = 1>) gathers every input pixel nine times from global memory, once per
 // filter tap, and re-applies the BatchNorm view each time: 13.9 GB fetched per launch for 1.38 GB of tensors, ~180 VALU

@@ -1,5 +1,5 @@
 // Weight gradient of the dense 3x3 stride-1 SAME convolution (DeepLabV3+ decoder, reference blocks.py:117,127), all nine taps in
-// ONE pass -- included by gemm.hip inside its anonymous namespace.
+// ONE pass -- included by conv3.hip inside its anonymous namespace.
 //
 //   dW[tap][k][n] = sum_m a[m + off(tap)][k] * dy[m][n]        a = act(s*x + t) (zero outside the image), dy = gview(g, y)
 //

@@ -1,4 +1,4 @@
-// Weight gradient of the dense 3x3 stride-1 SAME convolution (reference blocks.py:117) -- halo-tile form, included by gemm.hip
+// Weight gradient of the dense 3x3 stride-1 SAME convolution (reference blocks.py:117) -- halo-tile form, included by conv3.hip
 // inside its anonymous namespace.
 //
 //   dW[kh][kw][c][n] = sum_p a[p + (kh-1, kw-1)][c] * dy[p][n]  =  sum_q a[row + kh - 1][q][c] * dy[row][q - (kw - 1)][n]

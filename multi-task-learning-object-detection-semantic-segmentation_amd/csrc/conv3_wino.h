@@ -1,5 +1,5 @@
 // Dense 3x3 stride-1 SAME convolution (DeepLabV3+ decoder, reference blocks.py:117) forward and input gradient in the
-// WINOGRAD F(2x2, 3x3) form, fp32 throughout -- included by gemm.hip inside its anonymous namespace.
+// WINOGRAD F(2x2, 3x3) form, fp32 throughout -- included by conv3.hip inside its anonymous namespace.
 //
 // The halo-tile kernel (conv3_tile.h) runs the nine taps as nine MFMA passes over an LDS patch and sits at 0.85 of the fp32
 // MFMA peak: the arithmetic itself is what is left.  With 2x2 output tiles,

@@ -1,5 +1,5 @@
 // Dense 3x3 stride-1 SAME convolution (DeepLabV3+ decoder, reference blocks.py:117) forward and input gradient in the
-// WINOGRAD F(4x4, 3x3) form, fp32 throughout -- included by gemm.hip inside its anonymous namespace.
+// WINOGRAD F(4x4, 3x3) form, fp32 throughout -- included by conv3.hip inside its anonymous namespace.
 //
 //     Y = A^T [ sum_c (G w_c G^T) .* (B^T d_c B) ] A        B^T 6x6, G 6x3, A^T 4x6 (Lavin & Gray's matrices, below)
 // 4x4 output pixels per tile from a 6x6 input tile: the reduction over input channels becomes THIRTY-SIX independent GEMMs

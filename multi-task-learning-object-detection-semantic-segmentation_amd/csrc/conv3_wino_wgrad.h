@@ -1,5 +1,5 @@
 // Weight gradient of the dense 3x3 stride-1 SAME convolution (DeepLabV3+ decoder, reference blocks.py:117) in the WINOGRAD
-// F(2x2, 3x3) form, fp32 throughout -- included by gemm.hip inside its anonymous namespace, after conv3_wino.h.
+// F(2x2, 3x3) form, fp32 throughout -- included by conv3.hip inside its anonymous namespace, after conv3_wino.h.
 //
 // With Y = A^T [ sum_c U_c .* V_c ] A per 2x2 output tile (U = G w G^T, V = B^T d B, conv3_wino.h), the gradient of the loss
 // with respect to U is, per position k of the 4x4 grid, a plain GEMM over the TILES:

@@ -3,15 +3,11 @@
 //
 // dx[q][c] = sum_tap sum_o dY[q - d(tap)][o] * W[tap][c][o]: 36 multiply-adds per value from a 4-channel tensor that fits the L2
 // (9.8 MB at batch 32) -- a streaming layer: read the raw input of the BatchNorm in front (for its backward sums), write dx, 2 KB per
-// pixel.  As a tap-expanded GEMM (gemm.hip: dz = shift(dY) materialised, K = 36, N = 256, transposing epilogue that also reads the raw
+// pixel.  As a tap-expanded GEMM (conv3.hip: dz = shift(dY) materialised, K = 36, N = 256, transposing epilogue that also reads the raw
 // input) it ran 0.53 + 0.03 ms = 2.3 TB/s of that traffic; this kernel: 0.365 ms = 3.5 TB/s.  Here a wave is one pixel's 64 channel quads: the nine dY vectors of a pixel are
 // wave-uniform (scalar loads), the 36 x 4 weights of a lane stay in registers, a lane forms its four dx values, adds them into the
 // BatchNorm sums (sum mask dx, sum mask dx xhat: the same expressions as the GEMM epilogue's) and stores 16 bytes -- a wave stores 1 KB.
-#include "common.h"
-
-// bn.hip
-int ssdseg_bn_bwd_finalize_launch(ssdseg_ctx* ctx, const float* part, int nparts, int c, double count, const float* scale,
-                                  const float* mean, const float* invstd, float* dgamma, float* dbeta, float* k1, float* k0);
+#include "gemm_internal.h"
 
 namespace {
 
@@ -125,7 +121,7 @@ __global__ void __launch_bounds__(256) conv3n_bwd_bn_direct_kernel(C3NArgs p) {
 
 extern "C" {
 
-// (internal helpers of ssdseg_conv3x3_bwd_data_bn in gemm.hip, which declares them inside its extern "C" block)
+// (internal helpers of ssdseg_conv3x3_bwd_data_bn in conv3.hip, declared in gemm_internal.h)
 bool ssdseg_conv3n_direct_takes(int cin, int cout, int ldx) {
     const char* e = getenv("SSDSEG_CONV3N_DIRECT");      // "0": the tap-expanded GEMM (A/B runs, a parity-test case)
     if (e != nullptr && e[0] == '0') return false;

@@ -63,7 +63,6 @@ __device__ __forceinline__ float4 load_gview_if(const GViewDev& v, const ChanCoe
 __device__ __forceinline__ void fma4(float4& acc, float4 a, float4 b) {
     acc.x = fmaf(a.x, b.x, acc.x); acc.y = fmaf(a.y, b.y, acc.y); acc.z = fmaf(a.z, b.z, acc.z); acc.w = fmaf(a.w, b.w, acc.w);
 }
-__device__ __forceinline__ void add4(float4& acc, float4 a) { acc.x += a.x; acc.y += a.y; acc.z += a.z; acc.w += a.w; }
 
 // block-level reduction over threadIdx.y of one float4 per thread; result valid for threadIdx.y == 0
 __device__ __forceinline__ float4 reduce_over_y(float4 v, float4* red) {
@@ -345,11 +344,6 @@ bool dw_geometry(int n, int h, int w, int c, int stride, int dilation, DwGeom* g
 #include "dwconv_march.h"
 
 #include <stdlib.h>
-
-int ssdseg_colsum(ssdseg_ctx* ctx, const float* part, int nparts, long long len, float* out);  // bn.hip
-// bn.hip: (dgamma, dbeta, k1, k0) from nparts partial rows of (sum mask*g, sum mask*g*xhat)
-int ssdseg_bn_bwd_finalize_launch(ssdseg_ctx* ctx, const float* part, int nparts, int c, double count, const float* scale,
-                                  const float* mean, const float* invstd, float* dgamma, float* dbeta, float* k1, float* k0);
 
 namespace {
 

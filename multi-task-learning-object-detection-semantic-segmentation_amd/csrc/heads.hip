@@ -6,11 +6,8 @@
 //   SSD head gather: Reshape(-1,4) + Concatenate(axis=1) (blocks.py:155, models.py:256,271) and Softmax (models.py:259)
 #include "common.h"
 
-int ssdseg_colsum(ssdseg_ctx* ctx, const float* part, int nparts, long long len, float* out);
-
 namespace {
 
-__device__ __forceinline__ void add4(float4& a, float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
 __device__ __forceinline__ void axpy4(float4& a, float s, float4 b) {
     a.x = fmaf(s, b.x, a.x); a.y = fmaf(s, b.y, a.y); a.z = fmaf(s, b.z, a.z); a.w = fmaf(s, b.w, a.w);
 }

@@ -47,28 +47,6 @@ struct PwTArgs {
     unsigned a_bytes, wt_bytes;
 };
 
-// global -> LDS copy of 16 bytes per lane (buffer_load_dwordx4 ... lds), written as inline asm ON PURPOSE: through the builtin the
-// compiler's wait-count pass orders every later ds_read behind the pending LDS write (it cannot tell the two buffers apart) and
-// put `s_waitcnt vmcnt(<loads issued after the DMA>)` in front of the first fragment read of every step -- i.e. the prefetch was
-// waited for right after it was issued.  An asm statement is invisible to that pass; completion is OUR job: the DMA is older
-// than the step's register loads (the counter is in-order), commit() ends with an explicit vmcnt(0), and the barrier follows.
-// lds_byte_addr: wave-uniform LDS address of lane 0's 16 bytes (lane l lands at +16*l); M0 is saved and restored in the statement.
-typedef int pwt_i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ pwt_i32x4 pwt_make_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    pwt_i32x4 r;
-    r.x = (int)(unsigned)(a & 0xffffffffull);
-    r.y = (int)(unsigned)((a >> 32) & 0xffffull);     // stride 0
-    r.z = (int)bytes;                                    // num_records (bytes): offsets beyond it read zeros
-    r.w = 0x00020000;
-    return r;
-}
-__device__ __forceinline__ void lds_dma16(pwt_i32x4 rsrc, unsigned lds_byte_addr, unsigned voffset, int soffset) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(voffset), "s"(rsrc), "s"(soffset) : "memory");
-}
-
 // (rows, cols): 32 * waves-along-M, 32 * WN * waves-along-N
 constexpr size_t pwt_lds_floats(int rows, int cols, int cred) { return 2 * (size_t)(rows + cols) * PWT_KC + 4 * (size_t)((cred + 31) / 32 * 32 + PWT_KC); }
 

@@ -8,10 +8,10 @@
 // same addresses for all its lanes (one request), and the 27 x 4 weights of the thread live in registers for the whole kernel.  The
 // input rescale (x * s + o, zero padding AFTER it) is folded into the weights: sum_valid (x s + o) w = sum_valid x (s w) + sum_valid o w.
 // A block walks whole output rows (no per-pixel division); BatchNorm partial sums: one row per block, fixed order.
-#include "common.h"
+// Below the kernel: the ssdseg_stem_conv_* entry points, which choose between this kernel and the implicit GEMM.
+#include "gemm_internal.h"
 
 namespace {
-
 
 struct StemArgs {
     const float* x;      // [n][h][w][3]
@@ -127,15 +127,14 @@ __global__ void __launch_bounds__(256) stem_fwd_direct_kernel(StemArgs p) {
     }
 }
 
-inline void stem_pad(int size, int* out, int* before) {      // TF SAME, kernel 3, stride 2
-    *out = (size + 1) / 2;
-    const int total = (*out - 1) * 2 + 3 - size;
-    *before = (total > 0 ? total : 0) / 2;
+// TF SAME, kernel 3, stride 2
+void stem_geometry(int h, int wdt, int* ho, int* wo, int* pt, int* pl) {
+    same_pad(h, 3, 2, 1, ho, pt);
+    same_pad(wdt, 3, 2, 1, wo, pl);
 }
 
 }  // namespace
 
-// (internal helpers of ssdseg_stem_conv_fwd / ssdseg_stem_conv_parts in gemm.hip, which declares them inside its extern "C" block)
 extern "C" {
 
 // the direct kernel CAN take the layer (sizes the statistics table, whatever the environment says) / DOES take it
@@ -158,8 +157,7 @@ int ssdseg_stem_direct_fwd(ssdseg_ctx* ctx, const float* x, const float* w, cons
     StemArgs a{};
     a.x = x; a.w = w; a.bias = bias; a.y = y; a.stats = stats;
     a.n = n; a.h = h; a.w_ = wdt; a.cout = cout; a.scale = in_scale; a.offset = in_offset;
-    stem_pad(h, &a.ho, &a.pt);
-    stem_pad(wdt, &a.wo, &a.pl);
+    stem_geometry(h, wdt, &a.ho, &a.wo, &a.pt, &a.pl);
     a.x_bytes = (unsigned)((size_t)n * h * wdt * 12);
     const double m = (double)n * a.ho * a.wo;
     const double bytes = 4.0 * ((double)n * h * wdt * 3 + m * cout + 27.0 * cout), flops = 2.0 * m * 27 * cout;
@@ -175,4 +173,89 @@ int ssdseg_stem_direct_fwd(ssdseg_ctx* ctx, const float* x, const float* w, cons
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ stem (K1 + K2)
+// Rescaling + Conv2D 3x3 stride 2 SAME on the 3-channel image (reference models.py:187,196 -> :65; ShuffleNetV2 :622,628)
+// as implicit GEMM [n*ho*wo, 27] x [27, cout] through the MFMA kernels of gemm.hip (LD = 2): the im2col gather happens in the LDS
+// loader, the output leaves the accumulators as full 128-byte row segments, BN statistics come from the epilogue.
+int ssdseg_stem_conv_parts(int n, int h, int w, int cout, int* nparts_host) {
+    SSDSEG_ARG(n > 0 && h > 0 && w > 0, 1);
+    SSDSEG_ARG(cout > 0 && cout % 4 == 0, 4);
+    SSDSEG_ARG(nparts_host != nullptr, 5);
+    int ho, wo, pt, pl;
+    stem_geometry(h, w, &ho, &wo, &pt, &pl);
+    // (sized for whichever forward kernel may run: the direct one writes one row per block, the implicit GEMM one per grid row)
+    const int a = ssdseg_rowA_grid_y(n * ho * wo, cout), b = ssdseg_stem_direct_eligible(cout) ? ssdseg_stem_direct_blocks(n, h) : 0;
+    *nparts_host = a > b ? a : b;
+    return 0;
+}
+
+int ssdseg_stem_conv_fwd(ssdseg_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int n, int h, int wdt,
+                         int cin, int cout, float in_scale, float in_offset, float* stats) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    SSDSEG_ARG(x != nullptr, 2);
+    SSDSEG_ARG(w != nullptr, 3);
+    SSDSEG_ARG(bias == nullptr || stats == nullptr, 4);   // a biased conv is never followed by BatchNormalization here
+    SSDSEG_ARG(y != nullptr, 5);
+    SSDSEG_ARG(n > 0 && h > 0 && wdt > 0, 6);
+    SSDSEG_ARG(cin == 3, 9);
+    SSDSEG_ARG(cout > 0 && cout % 4 == 0, 10);
+    const bool direct = ssdseg_stem_direct_takes(cout) && (long long)n * h * wdt * 12 < (1LL << 31);      // (32-bit buffer offsets into the image)
+    if (stats != nullptr) {      // the table is sized for the larger of the two kernels' row counts: the rows this launch does not write are zero
+        int nparts = 0, ho_, wo_, pt_, pl_;
+        int rc = ssdseg_stem_conv_parts(n, h, wdt, cout, &nparts);
+        if (rc) return rc;
+        stem_geometry(h, wdt, &ho_, &wo_, &pt_, &pl_);
+        const int mine = direct ? ssdseg_stem_direct_blocks(n, h) : ssdseg_rowA_grid_y(n * ho_ * wo_, cout);
+        if (nparts > mine) SSDSEG_HIP(hipMemsetAsync(stats + (size_t)mine * 2 * cout, 0, (size_t)(nparts - mine) * 2 * cout * sizeof(float), ctx->stream));
+    }
+    if (direct) return ssdseg_stem_direct_fwd(ctx, x, w, bias, y, n, h, wdt, cout, in_scale, in_offset, stats);
+    ssdseg_rowa_args a{};
+    a.a0 = x; a.act = SSDSEG_ACT_NONE;
+    a.b = w; a.ldb = cout;
+    a.out = y; a.ldo = cout;
+    a.stats = stats;
+    a.bias = bias;
+    stem_geometry(h, wdt, &a.convH, &a.convW, &a.stemPt, &a.stemPl);
+    a.stemH = h; a.stemW = wdt; a.stemScale = in_scale; a.stemOffset = in_offset;
+    a.I = n * a.convH * a.convW; a.R = 27; a.J = cout;
+    return ssdseg_rowA_stem_fwd(ctx, a);
+}
+
+int ssdseg_stem_conv_bwd_weight(ssdseg_ctx* ctx, const float* x, const ssdseg_gview* dy, float* dw, float* dbias, int n, int h,
+                                int wdt, int cin, int cout, float in_scale, float in_offset) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    SSDSEG_ARG(x != nullptr, 2);
+    SSDSEG_ARG(dy != nullptr && dy->g != nullptr, 3);
+    SSDSEG_ARG(dy->scale == nullptr || (dy->y && dy->shift && dy->k1 && dy->k0), 3);
+    SSDSEG_ARG(dbias == nullptr || dy->scale == nullptr, 5);   // the bias gradient is the plain column sum of g
+    SSDSEG_ARG(dw != nullptr, 4);
+    SSDSEG_ARG(n > 0 && h > 0 && wdt > 0, 6);
+    SSDSEG_ARG(cin == 3, 9);
+    SSDSEG_ARG(cout > 0 && cout % 4 == 0, 10);
+    ssdseg_wgrad_args a{};
+    a.x = x; a.xact = SSDSEG_ACT_NONE;
+    a.g = dy->g; a.y = dy->y; a.gs = dy->scale; a.gt = dy->shift; a.gk1 = dy->k1; a.gk0 = dy->k0; a.gact = dy->act;
+    a.ldy = cout;
+    a.stem = 1;
+    stem_geometry(h, wdt, &a.convH, &a.convW, &a.stemPt, &a.stemPl);
+    a.stemH = h; a.stemW = wdt; a.stemScale = in_scale; a.stemOffset = in_offset;
+    a.M = n * a.convH * a.convW; a.K = 27; a.N = cout;
+    int rc = ssdseg_wgrad_run(ctx, a, dw);
+    if (rc || !dbias) return rc;
+    // dbias[c] = sum_m g[m][c]: per-block channel sums, then the fixed-order fold
+    int nparts = 0;
+    rc = ssdseg_channel_stats_parts(a.M, cout, &nparts);
+    if (rc) return rc;
+    void* ws;
+    rc = ssdseg_workspace(ctx, ((size_t)nparts * 2 * cout + 2 * (size_t)cout) * sizeof(float), &ws);
+    if (rc) return rc;
+    float* part = (float*)ws;
+    float* both = part + (size_t)nparts * 2 * cout;
+    rc = ssdseg_channel_stats(ctx, dy->g, cout, a.M, cout, part);
+    if (rc) return rc;
+    rc = ssdseg_colsum(ctx, part, nparts, 2LL * cout, both);
+    if (rc) return rc;
+    SSDSEG_HIP(hipMemcpyAsync(dbias, both, (size_t)cout * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    return 0;
+}
 }  // extern "C"

@@ -348,7 +348,7 @@ def test_bn_finalize_apply_bwd(ctx, guards, rng, m, c, parts):
     guards.check()
 
 
-@pytest.mark.parametrize("form", ["direct", "gemm"])      # csrc/stem.hip (default for <= 64 output channels) / the implicit GEMM of csrc/gemm.hip
+@pytest.mark.parametrize("form", ["direct", "gemm"])      # csrc/stem.hip (default for <= 64 output channels) / the implicit GEMM of csrc/gemm.hip, chosen in csrc/stem.hip
 @pytest.mark.parametrize("n,h,w,cout,bias", [(2, 48, 64, 32, False), (1, 15, 21, 24, True), (3, 480, 640, 32, False), (2, 33, 47, 40, False),
                                              (9, 480, 64, 32, False)])      # 2,160 output rows: more than the direct kernel's 2,048 blocks
 def test_stem_conv(ctx, guards, rng, monkeypatch, n, h, w, cout, bias, form):
