@@ -396,6 +396,23 @@ int ssdseg_flip_gt_boxes(ssdseg_ctx* ctx, float* gt, const int32_t* gt_count, co
  * The means are reduced in a fixed order (block partials in the ctx workspace): the result is the same bits on every run. */
 int ssdseg_rgb_augment(ssdseg_ctx* ctx, const uint8_t* images_u8, const uint8_t* flip, const float* draws4_host,
                        float* means, float* images_f32, int b, int h, int w);
+/* Device-resident training set (datacoder.ResidentDataset): the reference's NB03#cell8 chain -- shuffle(len), map(read_and_encode),
+ * batch, map(augmentation_rgb_channels) -- with the samples kept in HBM as the files hold them.  A batch is a list of pool sample
+ * indices and flip flags, both HOST arrays ([b] int32 / [b] uint8 or NULL) that are validated here (every index in [0, n_pool),
+ * else the argument error and nothing is launched) and passed to the kernels by value: no copy, no synchronisation, and the
+ * caller may overwrite them as soon as the call returns.
+ * ssdseg_gather_inputs: pool_images u8 [n_pool][h][w][3], pool_masks u8 [n_pool][h][w]; output sample n is pool sample
+ *   index_host[n], mirrored where flip_host[n] != 0: images_f32 [b][h][w][3] and mask_onehot [b][h][w][c] hold the bits
+ *   ssdseg_expand_inputs (datacoder.py:302-347) writes for the same samples stacked on the host -- or, with draws4_host != NULL,
+ *   the image and means [b][3] (device, out) the bits of ssdseg_rgb_augment (datacoder.py:434-466; same fixed reduction order).
+ *   Either pool / destination pair may be NULL; draws need the image pair and means.  Pool offsets are 64-bit.
+ * ssdseg_gather_gt: pool_gt [n_pool][gmax][5], pool_cnt [n_pool] -> gt [b][gmax][5], gt_count [b]; rows g < count of a flagged
+ *   sample mirrored as ssdseg_flip_gt_boxes does (xmin' = W - xmax, xmax' = W - xmin), rows past the count written as zeros. */
+int ssdseg_gather_inputs(ssdseg_ctx* ctx, const uint8_t* pool_images, const uint8_t* pool_masks, int n_pool, const int32_t* index_host,
+                         const uint8_t* flip_host, const float* draws4_host, float* means, float* images_f32, float* mask_onehot, int b, int h,
+                         int w, int c);
+int ssdseg_gather_gt(ssdseg_ctx* ctx, const float* pool_gt, const int32_t* pool_cnt, int n_pool, const int32_t* index_host,
+                     const uint8_t* flip_host, float* gt, int32_t* gt_count, int b, int gmax, float image_width);
 
 /* ---------------------------------------------------------------- training metrics
  * Per-image values of the three metric factories NB03#cell14 passes to compile(metrics=...); Keras averages them.

@@ -18,6 +18,12 @@
 //                          pixels straight into the engine's float32 input buffer, mirrored where flagged.  Float work: it follows
 //                          the host spec datacoder._augment_rgb operation for operation (no FMA contraction, correctly rounded
 //                          divisions), so it agrees with it to rounding (tests/test_gpu_rgb_augmentation.py).
+// And the reference's tf.data chain itself (NB03#cell8: shuffle(len) -> map(read_and_encode) -> batch -> map(augmentation)) for a
+// training set that lives in HBM (datacoder.ResidentDataset): indexed forms of the above that build a batch from pools,
+//   ssdseg_gather_inputs   output sample n = pool sample index[n], expanded (or colour-augmented) and mirrored where flagged:
+//                          the bits of ssdseg_expand_inputs / ssdseg_rgb_augment on the same samples stacked on the host;
+//   ssdseg_gather_gt       its ground-truth rows and count, mirrored as ssdseg_flip_gt_boxes does, rows past the count zero
+// (tests/test_gpu_resident_dataset.py).
 #include <cmath>
 
 #include "common.h"
@@ -125,11 +131,9 @@ __device__ __forceinline__ void load4px(const uint8_t* img, int p, float px[12])
 // pass 1: per block and channel, the sum of the hue- and saturation-adjusted values of its (up to) 1024 pixels of image
 // blockIdx.y, in a fixed order -> part[n][blockIdx.x][3].  Reads the pixels in storage order (the mean ignores the mirror).
 // VEC: every image row holds a multiple of 4 pixels.
+// (the body, shared with the gathering form below: `src` is the image, `part3` the block's 3 partial sums)
 template <bool VEC>
-__global__ void __launch_bounds__(AUG_THREADS) rgb_aug_stats_kernel(const uint8_t* __restrict__ img, float* __restrict__ part, int hw,
-                                                                     float hue, float sat) {
-    const int n = blockIdx.y;
-    const uint8_t* src = img + (long long)n * hw * 3;
+__device__ __forceinline__ void rgb_aug_stats_block(const uint8_t* __restrict__ src, float* __restrict__ part3, int hw, float hue, float sat) {
     const int p0 = blockIdx.x * AUG_BLOCK_PIX + threadIdx.x * AUG_PIX;
     float acc[3] = {0.f, 0.f, 0.f};
     if (VEC && p0 < hw) {
@@ -161,8 +165,15 @@ __global__ void __launch_bounds__(AUG_THREADS) rgb_aug_stats_kernel(const uint8_
         float t = 0.f;
 #pragma unroll
         for (int k = 0; k < AUG_THREADS / 64; ++k) t += red[k][threadIdx.x];
-        part[((long long)n * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = t;
+        part3[threadIdx.x] = t;
     }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(AUG_THREADS) rgb_aug_stats_kernel(const uint8_t* __restrict__ img, float* __restrict__ part, int hw,
+                                                                     float hue, float sat) {
+    const int n = blockIdx.y;
+    rgb_aug_stats_block<VEC>(img + (long long)n * hw * 3, part + ((long long)n * gridDim.x + blockIdx.x) * 3, hw, hue, sat);
 }
 
 // pass 2: means[n][c] = (sum of the nb block partials, in double, fixed order) / hw.  One wave per (channel, image).
@@ -177,15 +188,12 @@ __global__ void __launch_bounds__(64) rgb_aug_means_kernel(const float* __restri
 
 // pass 3: recompute the adjusted pixel from the uint8 input, contrast about the mean, brightness, clip; output pixel x of a
 // flagged image comes from source pixel w - 1 - x
+// (the body, shared with the gathering form below: `src` / `dst` are the image and its output, `mean3` its 3 means, `f` its flag)
 template <bool VEC>
-__global__ void __launch_bounds__(AUG_THREADS) rgb_aug_apply_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ flip,
-                                                                     const float* __restrict__ means, float* __restrict__ out, int h, int w,
-                                                                     float hue, float sat, float con, float bri) {
-    const int n = blockIdx.y, hw = h * w;
-    const uint8_t* src = img + (long long)n * hw * 3;
-    float* dst = out + (long long)n * hw * 3;
-    const bool f = flip != nullptr && flip[n] != 0;
-    const float m0 = means[n * 3], m1 = means[n * 3 + 1], m2 = means[n * 3 + 2];
+__device__ __forceinline__ void rgb_aug_apply_block(const uint8_t* __restrict__ src, float* __restrict__ dst, const float* __restrict__ mean3,
+                                                    bool f, int h, int w, float hue, float sat, float con, float bri) {
+    const int hw = h * w;
+    const float m0 = mean3[0], m1 = mean3[1], m2 = mean3[2];
     const int p0 = blockIdx.x * AUG_BLOCK_PIX + threadIdx.x * AUG_PIX;
     if (VEC) {
         if (p0 >= hw) return;
@@ -220,6 +228,148 @@ __global__ void __launch_bounds__(AUG_THREADS) rgb_aug_apply_kernel(const uint8_
             dst[p * 3 + 2] = contrast_brightness(b, m2, con, bri);
         }
     }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(AUG_THREADS) rgb_aug_apply_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ flip,
+                                                                     const float* __restrict__ means, float* __restrict__ out, int h, int w,
+                                                                     float hue, float sat, float con, float bri) {
+    const int n = blockIdx.y;
+    const long long off = (long long)n * h * w * 3;
+    rgb_aug_apply_block<VEC>(img + off, out + off, means + n * 3, flip != nullptr && flip[n] != 0, h, w, hue, sat, con, bri);
+}
+
+// ---------------------------------------------------------------- device-resident training set (datacoder.ResidentDataset)
+// The samples stay in HBM as the files hold them (pools of uint8 pixels, uint8 class indices, ground-truth rows); a batch is a
+// list of sample indices + flip flags drawn on the host each epoch (NB03#cell8: shuffle, read_and_encode, batch).  The list
+// travels BY VALUE in the kernel arguments, GATHER_CHUNK samples per launch: no host -> device copy of its own, nothing the
+// caller could overwrite while it is in flight, no synchronisation.  blockIdx.y is the sample within the chunk (wave-uniform
+// reads of the argument block); all pool offsets are 64-bit (index * h * w * 3 passes 2^32 at 4,661 samples of 480x640).
+constexpr int GATHER_CHUNK = 64;
+struct gather_sel {
+    int32_t index[GATHER_CHUNK];     // pool sample of output sample n0 + n
+    unsigned long long flip;         // bit n: mirror it
+};
+
+// ssdseg_expand_inputs' work on gathered samples.  VEC (w % 4 == 0, aligned buffers): four consecutive output pixels per thread
+// -- 3 dwords of pixels + 1 dword of class indices in, 3 + c float4 out; mirrored, they are the 4 source pixels ending at
+// w - 1 - x, reversed.  Otherwise one pixel per thread, as expand_inputs_kernel.
+template <bool VEC>
+__global__ void __launch_bounds__(256) gather_expand_kernel(const uint8_t* __restrict__ pool_img, const uint8_t* __restrict__ pool_midx,
+                                                            gather_sel sel, float* __restrict__ out_img, float* __restrict__ out_mask, int n0, int h,
+                                                            int w, int c) {
+    const int n = blockIdx.y, hw = h * w;
+    const long long s = sel.index[n];
+    const bool f = ((sel.flip >> n) & 1ull) != 0;
+    const long long o = (long long)(n0 + n) * hw;          // first output pixel of this sample
+    if (VEC) {
+        const int p0 = (blockIdx.x * 256 + threadIdx.x) * 4;
+        if (p0 >= hw) return;
+        const int y = p0 / w, x = p0 - y * w;
+        const int sp = y * w + (f ? w - 4 - x : x);
+        if (pool_img != nullptr) {
+            float px[12], q[12];
+            load4px(pool_img + s * hw * 3, sp, px);
+#pragma unroll
+            for (int j = 0; j < 12; ++j) q[j] = f ? px[3 * (3 - j / 3) + j % 3] : px[j];
+            float* d = out_img + (o + p0) * 3;
+            st4(d, make_float4(q[0], q[1], q[2], q[3]));
+            st4(d + 4, make_float4(q[4], q[5], q[6], q[7]));
+            st4(d + 8, make_float4(q[8], q[9], q[10], q[11]));
+        }
+        if (pool_midx != nullptr) {
+            uint32_t m = *reinterpret_cast<const uint32_t*>(pool_midx + s * hw + sp);
+            if (f) m = __builtin_bswap32(m);
+            float* d = out_mask + (o + p0) * c;
+            if (c == 4) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int k = (int)((m >> (8 * j)) & 0xffu);
+                    st4(d + 4 * j, make_float4(k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f, k == 3 ? 1.f : 0.f));
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int k = (int)((m >> (8 * j)) & 0xffu);
+                    for (int t = 0; t < c; ++t) d[j * c + t] = k == t ? 1.f : 0.f;
+                }
+            }
+        }
+    } else {
+        const int p = blockIdx.x * 256 + threadIdx.x;
+        if (p >= hw) return;
+        const int y = p / w, x = p - y * w;
+        const int sp = y * w + (f ? w - 1 - x : x);
+        if (pool_img != nullptr) {
+            const uint8_t* r = pool_img + (s * hw + sp) * 3;
+            float* d = out_img + (o + p) * 3;
+            d[0] = (float)r[0]; d[1] = (float)r[1]; d[2] = (float)r[2];
+        }
+        if (pool_midx != nullptr) {
+            const int k = pool_midx[s * hw + sp];
+            float* d = out_mask + (o + p) * c;
+            for (int t = 0; t < c; ++t) d[t] = k == t ? 1.f : 0.f;
+        }
+    }
+}
+
+// ssdseg_rgb_augment's passes 1 and 3 on gathered samples: the same block bodies on the same pixels, so the same partial sums,
+// the same means (pass 2 is rgb_aug_means_kernel itself, once for the batch) and the same output bits
+template <bool VEC>
+__global__ void __launch_bounds__(AUG_THREADS) gather_rgb_stats_kernel(const uint8_t* __restrict__ pool_img, gather_sel sel, float* __restrict__ part,
+                                                                        int n0, int hw, float hue, float sat) {
+    const int n = blockIdx.y;
+    rgb_aug_stats_block<VEC>(pool_img + (long long)sel.index[n] * hw * 3, part + ((long long)(n0 + n) * gridDim.x + blockIdx.x) * 3, hw, hue, sat);
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(AUG_THREADS) gather_rgb_apply_kernel(const uint8_t* __restrict__ pool_img, gather_sel sel,
+                                                                        const float* __restrict__ means, float* __restrict__ out, int n0, int h, int w,
+                                                                        float hue, float sat, float con, float bri) {
+    const int n = blockIdx.y;
+    rgb_aug_apply_block<VEC>(pool_img + (long long)sel.index[n] * h * w * 3, out + (long long)(n0 + n) * h * w * 3, means + (n0 + n) * 3,
+                             ((sel.flip >> n) & 1ull) != 0, h, w, hue, sat, con, bri);
+}
+
+// ground-truth rows and counts of the gathered samples; rows g < count of a flagged sample mirrored as flip_gt_boxes_kernel does,
+// rows past the count zero
+__global__ void __launch_bounds__(64) gather_gt_kernel(const float* __restrict__ pool_gt, const int32_t* __restrict__ pool_cnt, gather_sel sel,
+                                                       float* __restrict__ gt, int32_t* __restrict__ gt_count, int n0, int gmax, float width) {
+    const int n = blockIdx.y, g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= gmax) return;
+    const long long s = sel.index[n];
+    const bool f = ((sel.flip >> n) & 1ull) != 0;
+    const int cnt = pool_cnt[s];
+    if (g == 0) gt_count[n0 + n] = cnt;
+    const float* r = pool_gt + (s * gmax + g) * 5;             // (label, xmin, ymin, xmax, ymax)
+    float* o = gt + ((long long)(n0 + n) * gmax + g) * 5;
+    if (g < cnt) {
+        const float xmin = r[1], xmax = r[3];
+        o[0] = r[0];
+        o[1] = f ? width - xmax : xmin;
+        o[2] = r[2];
+        o[3] = f ? width - xmin : xmax;
+        o[4] = r[4];
+    } else {
+        o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; o[4] = 0.f;
+    }
+}
+
+// samples [n0, n0 + count) of the host lists as one kernel-argument block
+gather_sel make_sel(const int32_t* index_host, const uint8_t* flip_host, int n0, int count) {
+    gather_sel sel;
+    memset(&sel, 0, sizeof(sel));
+    for (int i = 0; i < count; ++i) {
+        sel.index[i] = index_host[n0 + i];
+        if (flip_host != nullptr && flip_host[n0 + i] != 0) sel.flip |= 1ull << i;
+    }
+    return sel;
+}
+
+bool indices_in_pool(const int32_t* index_host, int b, int n_pool) {
+    for (int i = 0; i < b; ++i)
+        if (index_host[i] < 0 || index_host[i] >= n_pool) return false;
+    return true;
 }
 
 }  // namespace
@@ -288,6 +438,108 @@ int ssdseg_rgb_augment(ssdseg_ctx* ctx, const uint8_t* images_u8, const uint8_t*
         SSDSEG_LAUNCH(ctx, 15.0 * px + 12.0 * b, 0.0, rgb_aug_apply_kernel<false>, dim3(nb, b), dim3(AUG_THREADS), 0, images_u8, flip, means, images_f32,
                       h, w, hue, sat, con, bri);
     SSDSEG_LAUNCH_CHECK();
+    return 0;
+}
+
+int ssdseg_gather_inputs(ssdseg_ctx* ctx, const uint8_t* pool_images, const uint8_t* pool_masks, int n_pool, const int32_t* index_host,
+                         const uint8_t* flip_host, const float* draws4_host, float* means, float* images_f32, float* mask_onehot, int b, int h,
+                         int w, int c) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    SSDSEG_ARG(pool_images != nullptr || pool_masks != nullptr, 2);
+    SSDSEG_ARG(n_pool > 0, 4);
+    SSDSEG_ARG(index_host != nullptr, 5);
+    SSDSEG_ARG(draws4_host == nullptr || pool_images != nullptr, 7);
+    SSDSEG_ARG(draws4_host == nullptr ||
+               (std::isfinite(draws4_host[0]) && std::isfinite(draws4_host[1]) && std::isfinite(draws4_host[2]) && std::isfinite(draws4_host[3])), 7);
+    SSDSEG_ARG(draws4_host == nullptr || means != nullptr, 8);
+    SSDSEG_ARG(pool_images == nullptr || images_f32 != nullptr, 9);
+    SSDSEG_ARG(pool_masks == nullptr || mask_onehot != nullptr, 10);
+    SSDSEG_ARG(b > 0 && h > 0 && w > 0, 11);
+    SSDSEG_ARG((long long)h * w * 3 < (1LL << 31), 12);      // in-image pixel and byte offsets in 32 bits
+    SSDSEG_ARG(c > 0 && c <= 8, 14);
+    SSDSEG_ARG(indices_in_pool(index_host, b, n_pool), 5);
+    const int hw = h * w;
+    const bool colour = draws4_host != nullptr;
+    // dword loads and float4 stores: whole groups of 4 pixels per row and aligned buffers
+    const bool vec = w % 4 == 0 && (pool_images == nullptr || (((uintptr_t)pool_images & 3) == 0 && ((uintptr_t)images_f32 & 15) == 0)) &&
+                     (pool_masks == nullptr || (((uintptr_t)pool_masks & 3) == 0 && ((uintptr_t)mask_onehot & 15) == 0));
+    const int nb = cdiv(hw, AUG_BLOCK_PIX);
+    float hue = 0.f, sat = 1.f, con = 1.f, bri = 0.f;
+    float* part = nullptr;
+    if (colour) {
+        hue = draws4_host[0]; sat = draws4_host[1]; con = draws4_host[2]; bri = draws4_host[3];
+        void* ws = nullptr;
+        int rc = ssdseg_workspace(ctx, (size_t)b * nb * 3 * sizeof(float), &ws);
+        if (rc) return rc;
+        part = static_cast<float*>(ws);
+    }
+    // the plain expansion: both halves, or only the mask when the image comes from the colour passes
+    const uint8_t* ex_img = colour ? nullptr : pool_images;
+    if (ex_img != nullptr || pool_masks != nullptr) {
+        const int gx = vec ? cdiv(hw, 1024) : cdiv(hw, 256);
+        for (int n0 = 0; n0 < b; n0 += GATHER_CHUNK) {
+            const int count = b - n0 < GATHER_CHUNK ? b - n0 : GATHER_CHUNK;
+            const gather_sel sel = make_sel(index_host, flip_host, n0, count);
+            const double bytes = (double)count * hw * ((ex_img ? 3.0 + 12.0 : 0.0) + (pool_masks ? 1.0 + 4.0 * c : 0.0));
+            if (vec)
+                SSDSEG_LAUNCH(ctx, bytes, 0.0, gather_expand_kernel<true>, dim3(gx, count), dim3(256), 0, ex_img, pool_masks, sel, images_f32, mask_onehot,
+                              n0, h, w, c);
+            else
+                SSDSEG_LAUNCH(ctx, bytes, 0.0, gather_expand_kernel<false>, dim3(gx, count), dim3(256), 0, ex_img, pool_masks, sel, images_f32,
+                              mask_onehot, n0, h, w, c);
+            SSDSEG_LAUNCH_CHECK();
+        }
+    }
+    if (!colour) return 0;
+    for (int n0 = 0; n0 < b; n0 += GATHER_CHUNK) {
+        const int count = b - n0 < GATHER_CHUNK ? b - n0 : GATHER_CHUNK;
+        const gather_sel sel = make_sel(index_host, nullptr, n0, count);       // the mean ignores the mirror
+        const double bytes = 3.0 * count * hw + 12.0 * count * nb;
+        if (vec)
+            SSDSEG_LAUNCH(ctx, bytes, 0.0, gather_rgb_stats_kernel<true>, dim3(nb, count), dim3(AUG_THREADS), 0, pool_images, sel, part, n0, hw, hue, sat);
+        else
+            SSDSEG_LAUNCH(ctx, bytes, 0.0, gather_rgb_stats_kernel<false>, dim3(nb, count), dim3(AUG_THREADS), 0, pool_images, sel, part, n0, hw, hue, sat);
+        SSDSEG_LAUNCH_CHECK();
+    }
+    for (int n0 = 0; n0 < b; n0 += 65535) {                                     // one grid row per image
+        const int count = b - n0 < 65535 ? b - n0 : 65535;
+        SSDSEG_LAUNCH(ctx, 12.0 * count * nb + 12.0 * count, 0.0, rgb_aug_means_kernel, dim3(3, count), dim3(64), 0, part + (size_t)n0 * nb * 3,
+                      means + (size_t)n0 * 3, nb, hw);
+        SSDSEG_LAUNCH_CHECK();
+    }
+    for (int n0 = 0; n0 < b; n0 += GATHER_CHUNK) {
+        const int count = b - n0 < GATHER_CHUNK ? b - n0 : GATHER_CHUNK;
+        const gather_sel sel = make_sel(index_host, flip_host, n0, count);
+        const double bytes = 15.0 * count * hw + 12.0 * count;
+        if (vec)
+            SSDSEG_LAUNCH(ctx, bytes, 0.0, gather_rgb_apply_kernel<true>, dim3(nb, count), dim3(AUG_THREADS), 0, pool_images, sel, means, images_f32, n0,
+                          h, w, hue, sat, con, bri);
+        else
+            SSDSEG_LAUNCH(ctx, bytes, 0.0, gather_rgb_apply_kernel<false>, dim3(nb, count), dim3(AUG_THREADS), 0, pool_images, sel, means, images_f32, n0,
+                          h, w, hue, sat, con, bri);
+        SSDSEG_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+int ssdseg_gather_gt(ssdseg_ctx* ctx, const float* pool_gt, const int32_t* pool_cnt, int n_pool, const int32_t* index_host,
+                     const uint8_t* flip_host, float* gt, int32_t* gt_count, int b, int gmax, float image_width) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    SSDSEG_ARG(pool_gt != nullptr, 2);
+    SSDSEG_ARG(pool_cnt != nullptr, 3);
+    SSDSEG_ARG(n_pool > 0, 4);
+    SSDSEG_ARG(index_host != nullptr, 5);
+    SSDSEG_ARG(gt != nullptr, 7);
+    SSDSEG_ARG(gt_count != nullptr, 8);
+    SSDSEG_ARG(b > 0 && gmax > 0, 9);
+    SSDSEG_ARG(indices_in_pool(index_host, b, n_pool), 5);
+    for (int n0 = 0; n0 < b; n0 += GATHER_CHUNK) {
+        const int count = b - n0 < GATHER_CHUNK ? b - n0 : GATHER_CHUNK;
+        const gather_sel sel = make_sel(index_host, flip_host, n0, count);
+        SSDSEG_LAUNCH(ctx, (40.0 * gmax + 8.0) * count, 0.0, gather_gt_kernel, dim3(cdiv(gmax, 64), count), dim3(64), 0, pool_gt, pool_cnt, sel, gt,
+                      gt_count, n0, gmax, image_width);
+        SSDSEG_LAUNCH_CHECK();
+    }
     return 0;
 }
 

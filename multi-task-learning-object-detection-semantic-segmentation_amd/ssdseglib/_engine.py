@@ -1632,9 +1632,9 @@ def run_predict(model: K.Model, data) -> List[np.ndarray]:
 
 
 def run_train_on_batch(model: K.Model, x, y=None) -> Dict[str, float]:
-    if _is_compact(x):
+    if _is_compact(x) or _is_resident(x):
         eng = engine_for(model, len(x), True)
-        ld = _compact_loader(eng, x)
+        ld = _batch_loader(eng, x)
         ld.stage(x)
         ld.consume()
         eng.train_step(optimizer=model._compiled.get("optimizer"))
@@ -1689,6 +1689,21 @@ class _BatchStager:
         self.staged = False
 
 
+def _encoder_anchors(ctx, encoder, det, mask_op):
+    """the encoder's default boxes on the device, after checking its anchor and class counts against the model's heads"""
+    corners = np.stack([encoder.xmin_boxes_default, encoder.ymin_boxes_default, encoder.xmax_boxes_default, encoder.ymax_boxes_default], axis=1)
+    anchors = ctx.array(corners.astype(np.float32))
+    if det is not None and anchors.shape[0] != det.y_boxes.shape[1]:
+        raise ValueError(f"encoder has {anchors.shape[0]} default boxes, the model's heads {det.y_boxes.shape[1]}")
+    # ssdseg_encode_targets writes (batch, anchors, encoder.num_classes) floats into the labels target and the mask is
+    # expanded to encoder.num_classes planes (reference datacoder.py:332): both buffers are sized by the MODEL's channels
+    if det is not None and int(encoder.num_classes) != det.y_labels.shape[-1]:
+        raise ValueError(f"encoder.num_classes = {encoder.num_classes}, the model's labels head has {det.y_labels.shape[-1]} classes")
+    if mask_op is not None and int(encoder.num_classes) != mask_op.y_true.shape[-1]:
+        raise ValueError(f"encoder.num_classes = {encoder.num_classes}, the model's mask head has {mask_op.y_true.shape[-1]} classes")
+    return anchors
+
+
 class _CompactLoader:
     """A `datacoder.CompactBatch` into the engine's input / target buffers (reference datacoder.py:302-347 == csrc/inputs.hip +
     ssdseg_encode_targets).  stage(): 39 MB of uint8 pixels / class indices / ground-truth rows go up on the copy stream (under
@@ -1710,16 +1725,7 @@ class _CompactLoader:
         self.gt = ctx.empty((b, self.GMAX, 5))
         self.cnt = ctx.empty(b, np.int32)
         self.means = ctx.empty((b, 3))      # per-(image, channel) means of the colour augmentation's contrast step
-        corners = np.stack([encoder.xmin_boxes_default, encoder.ymin_boxes_default, encoder.xmax_boxes_default, encoder.ymax_boxes_default], axis=1)
-        self.anchors = ctx.array(corners.astype(np.float32))
-        if self.det is not None and self.anchors.shape[0] != self.det.y_boxes.shape[1]:
-            raise ValueError(f"encoder has {self.anchors.shape[0]} default boxes, the model's heads {self.det.y_boxes.shape[1]}")
-        # ssdseg_encode_targets writes (batch, anchors, encoder.num_classes) floats into the labels target and the mask is
-        # expanded to encoder.num_classes planes (reference datacoder.py:332): both buffers are sized by the MODEL's channels
-        if self.det is not None and int(encoder.num_classes) != self.det.y_labels.shape[-1]:
-            raise ValueError(f"encoder.num_classes = {encoder.num_classes}, the model's labels head has {self.det.y_labels.shape[-1]} classes")
-        if self.mask_op is not None and int(encoder.num_classes) != self.mask_op.y_true.shape[-1]:
-            raise ValueError(f"encoder.num_classes = {encoder.num_classes}, the model's mask head has {self.mask_op.y_true.shape[-1]} classes")
+        self.anchors = _encoder_anchors(ctx, encoder, self.det, self.mask_op)
         self.staged = None
         self.draws = None
         self._keep = None
@@ -1774,8 +1780,68 @@ def _compact_loader(eng: "Engine", cb) -> _CompactLoader:
     return ld
 
 
+class _ResidentLoader:
+    """A `datacoder.ResidentBatch` into the engine's input / target buffers: the samples are already in HBM (the dataset's pools),
+    the batch is a list of indices, flip flags and colour draws.  stage() keeps the list; consume() builds the batch on the main
+    stream -- ssdseg_gather_inputs (expansion or colour augmentation, mirrored where flagged), ssdseg_gather_gt (rows, counts,
+    mirrored boxes), ssdseg_encode_targets -- with the bits _CompactLoader gives for `dataset.to_compact(batch)`.  Nothing is
+    uploaded and nothing waits."""
+
+    GMAX = _CompactLoader.GMAX
+
+    def __init__(self, eng: "Engine", encoder):
+        self.eng, self.ctx, self.enc = eng, eng.ctx, encoder
+        ctx, b = eng.ctx, eng.batch
+        ops = {kind: op for _, op, kind in eng._loss_names}
+        self.mask_op, self.det = ops.get("mask"), ops.get("conf") or ops.get("loc")
+        self.gt = ctx.empty((b, self.GMAX, 5))
+        self.cnt = ctx.empty(b, np.int32)
+        self.means = ctx.empty((b, 3))
+        self.anchors = _encoder_anchors(ctx, encoder, self.det, self.mask_op)
+        self.staged = None
+
+    def stage(self, rb) -> None:
+        b, ins, ds = self.eng.batch, self.eng.input_store, rb.dataset
+        if len(rb) != b or (ds.height, ds.width) != (ins.h, ins.w):
+            raise ValueError(f"resident batch of {len(rb)} samples of {ds.height}x{ds.width} for an engine of batch {b}, {ins.h}x{ins.w}")
+        if ds.ctx is not self.ctx or ds.GMAX != self.GMAX:
+            raise ValueError("resident dataset lives on another context than the model's engine")
+        self.staged = rb
+
+    def consume(self) -> None:
+        assert self.staged is not None
+        rb, ctx, b, ins, enc = self.staged, self.ctx, self.eng.batch, self.eng.input_store, self.enc
+        ds = rb.dataset
+        index = rb.index.ctypes.data
+        flip = rb.flip.ctypes.data if rb.flip is not None and rb.flip.any() else None
+        draws = (C.c_float * 4)(*rb.rgb_draws) if rb.rgb_draws is not None else None
+        c = self.mask_op.y_true.shape[-1] if self.mask_op is not None else 1
+        ctx.call("ssdseg_gather_inputs", ds.images, ds.masks if self.mask_op is not None else None, ds.num_samples, index, flip, draws,
+                 self.means if draws is not None else None, ins.buf, self.mask_op.y_true if self.mask_op is not None else None, b, ins.h, ins.w, c)
+        if self.det is not None:
+            ctx.call("ssdseg_gather_gt", ds.gt, ds.cnt, ds.num_samples, index, flip, self.gt, self.cnt, b, self.GMAX, float(ins.w))
+            ctx.call("ssdseg_encode_targets", self.anchors, self.anchors.shape[0], self.gt, self.cnt, b, self.GMAX, enc.num_classes,
+                     float(enc.iou_threshold), (C.c_float * 4)(*enc._stds), self.det.y_labels, self.det.y_boxes, None)
+        self.staged = None
+
+
+def _resident_loader(eng: "Engine", rb) -> _ResidentLoader:
+    ld = eng.__dict__.get("_resident_loader")
+    if ld is None or ld.enc is not rb.encoder:
+        ld = eng.__dict__["_resident_loader"] = _ResidentLoader(eng, rb.encoder)
+    return ld
+
+
 def _is_compact(x) -> bool:
     return type(x).__name__ == "CompactBatch"
+
+
+def _is_resident(x) -> bool:
+    return type(x).__name__ == "ResidentBatch"
+
+
+def _batch_loader(eng: "Engine", x):
+    return _resident_loader(eng, x) if _is_resident(x) else _compact_loader(eng, x)
 
 
 class History:
@@ -1797,10 +1863,10 @@ def run_fit(model: K.Model, data, epochs=1, validation_data=None, verbose=0) -> 
         staged_for = None      # id of the batch whose upload is in flight, and its stager
         while cur is not None:
             x, y = cur
-            n = len(x) if _is_compact(x) else (int(np.shape(x)[0]) if not isinstance(x, H.DeviceBuffer) else x.shape[0])
+            n = len(x) if _is_compact(x) or _is_resident(x) else (int(np.shape(x)[0]) if not isinstance(x, H.DeviceBuffer) else x.shape[0])
             eng = engine_for(model, n, True)
-            if _is_compact(x):
-                ld = _compact_loader(eng, x)
+            if _is_compact(x) or _is_resident(x):
+                ld = _batch_loader(eng, x)          # a resident batch has nothing to upload: it is never staged ahead
                 if not (staged_for is not None and staged_for[0] is cur):
                     ld.stage(x)
                 ld.consume()                        # expansion + anchor encoding on the device
@@ -1817,7 +1883,7 @@ def run_fit(model: K.Model, data, epochs=1, validation_data=None, verbose=0) -> 
                 ld = _compact_loader(eng, nxt[0])
                 ld.stage(nxt[0])                    # 39 MB on the copy stream, under the step just queued
                 staged_for = (nxt, ld)
-            elif overlap and nxt is not None and not _is_compact(nxt[0]) and nxt[1] is not None and not isinstance(nxt[0], H.DeviceBuffer) and int(np.shape(nxt[0])[0]) == n:
+            elif overlap and nxt is not None and not _is_compact(nxt[0]) and not _is_resident(nxt[0]) and nxt[1] is not None and not isinstance(nxt[0], H.DeviceBuffer) and int(np.shape(nxt[0])[0]) == n:
                 stager = eng.__dict__.setdefault("_stager", None) or _BatchStager(eng)
                 eng._stager = stager
                 if stager.stage(nxt[0], nxt[1]):
@@ -1832,10 +1898,10 @@ def run_fit(model: K.Model, data, epochs=1, validation_data=None, verbose=0) -> 
             vs: Dict[str, float] = {}
             vseen = 0
             for x, y in _batches(validation_data):
-                if _is_compact(x):
+                if _is_compact(x) or _is_resident(x):
                     n = len(x)
                     eng = eval_engine_for(model, n)
-                    ld = _compact_loader(eng, x)
+                    ld = _batch_loader(eng, x)
                     ld.stage(x)
                     ld.consume()                    # expansion (+ colour augmentation) + anchor encoding on the device
                 else:

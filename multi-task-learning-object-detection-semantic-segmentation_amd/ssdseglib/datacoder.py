@@ -255,6 +255,146 @@ def augmentation_rgb_channels(image_batch, targets_batch):
     return _augment_rgb(image_batch, *draws), targets_batch
 
 
+# ---- device-resident training set: NB03#cell8's shuffle / map(read_and_encode) / batch / map(augmentation) chain per epoch
+_RGB_RANGES = ((-0.05, 0.05), (0.95, 1.05), (0.90, 1.10), (-0.10, 0.10))     # the ranges of _draw_rgb (reference datacoder.py:452-461)
+
+
+def _epoch_plan(rng, num_samples: int, batch_size: int, shuffle: bool, flip: bool, rgb_augmentation: bool, drop_remainder: bool):
+    """One epoch of the reference's input chain as host lists, no device access: [(index int32 (b,), flip uint8 (b,) or None,
+    rgb draws (4 floats) or None)].  A fresh uniform permutation of the SAMPLES (`.shuffle(buffer_size=len)`), a fresh flip draw
+    per sample (`uniform >= 0.5`, reference datacoder.py:337-345), batches cut afterwards with the last partial one kept unless
+    drop_remainder, one colour draw set per batch (`.batch(B).map(augmentation_rgb_channels)`)."""
+    order = rng.permutation(num_samples) if shuffle else np.arange(num_samples)
+    order = order.astype(np.int32)
+    flips = (rng.uniform(0.0, 1.0, num_samples) >= 0.5).astype(np.uint8) if flip else None
+    plan = []
+    for lo in range(0, num_samples, batch_size):
+        hi = min(lo + batch_size, num_samples)
+        if drop_remainder and hi - lo < batch_size:
+            break
+        draws = tuple(float(rng.uniform(a, b)) for a, b in _RGB_RANGES) if rgb_augmentation else None
+        plan.append((order[lo:hi].copy(), None if flips is None else flips[lo:hi].copy(), draws))
+    return plan
+
+
+class ResidentBatch:
+    """A batch of a ResidentDataset: which samples (`index`, int32), which of them mirrored (`flip`, uint8 or None) and the colour
+    draws (`rgb_draws` or None) -- a few host bytes; the pixels stay on the device.  `Model.fit` / `train_on_batch` accept it."""
+
+    def __init__(self, dataset: "ResidentDataset", index, flip=None, rgb_draws=None):
+        self.dataset = dataset
+        self.index = np.ascontiguousarray(index, np.int32).reshape(-1)
+        if self.index.size == 0:
+            raise ValueError("resident batch: no samples")
+        if self.index.min() < 0 or self.index.max() >= dataset.num_samples:
+            raise IndexError(f"resident batch: sample index outside [0, {dataset.num_samples})")
+        self.flip = None if flip is None else np.ascontiguousarray(flip, np.uint8).reshape(-1)
+        if self.flip is not None and self.flip.size != self.index.size:
+            raise ValueError("resident batch: one flip flag per sample")
+        self.rgb_draws = _check_rgb_draws(rgb_draws)
+
+    @property
+    def encoder(self):
+        return self.dataset.encoder
+
+    def __len__(self):
+        return int(self.index.size)
+
+
+class ResidentDataset:
+    """A training set kept in device memory as the files hold it -- uint8 pixels, uint8 class indices, ground-truth rows: 1.2 MB per
+    480x640 sample -- uploaded once.  Iterating it is ONE EPOCH of the reference's chain (NB03#cell8:
+    `.shuffle(len).map(read_and_encode).batch(B).map(augmentation_rgb_channels)`): a new permutation of the samples, a new flip
+    draw per sample when `encoder.augmentation_horizontal_flip`, one colour draw set per batch when `rgb_augmentation`, the last
+    partial batch kept unless `drop_remainder` -- all from the dataset's own Generator(seed); TF's RNG streams are not reproduced.
+    The batches are `ResidentBatch` objects: `Model.fit(ds, epochs=N)` builds each one on the device (ssdseg_gather_inputs,
+    ssdseg_gather_gt, ssdseg_encode_targets), so after the upload no pixel crosses PCIe and the host does no per-sample work.
+    `samples`: an iterable of `read_compact` tuples (their flip flag is ignored); `capacity`: slots to allocate (default: the number
+    of samples), filled with `append` / `write` without holding the set on the host."""
+
+    GMAX = 64       # ground-truth rows per sample, as the compact loader (the encode kernel holds them in LDS)
+
+    def __init__(self, encoder: "DataEncoderDecoder", samples=None, *, capacity: Optional[int] = None, batch_size: int = 16,
+                 shuffle: bool = True, rgb_augmentation: bool = False, drop_remainder: bool = False, seed=None):
+        samples = list(samples) if samples is not None else []
+        capacity = len(samples) if capacity is None else int(capacity)
+        if capacity <= 0 or capacity < len(samples):
+            raise ValueError(f"resident dataset: capacity {capacity} for {len(samples)} samples")
+        if int(batch_size) <= 0:
+            raise ValueError("resident dataset: batch_size must be positive")
+        self.encoder = encoder
+        self.capacity, self.batch_size = capacity, int(batch_size)
+        self.shuffle, self.rgb_augmentation, self.drop_remainder = bool(shuffle), bool(rgb_augmentation), bool(drop_remainder)
+        self.height, self.width = int(encoder.image_height), int(encoder.image_width)
+        self.num_samples = 0
+        self._rng = np.random.default_rng(seed)
+        self.ctx = self.images = self.masks = self.gt = self.cnt = None
+        for sample in samples:
+            self.append(*sample[:3])
+
+    def _allocate(self) -> None:
+        """the four pools, on the first write (planning an epoch needs no device)"""
+        from . import _engine
+        self.ctx = ctx = _engine.default_context()
+        self.images = ctx.empty((self.capacity, self.height, self.width, 3), np.uint8)
+        self.masks = ctx.empty((self.capacity, self.height, self.width), np.uint8)
+        self.gt = ctx.empty((self.capacity, self.GMAX, 5))
+        self.cnt = ctx.empty(self.capacity, np.int32)
+
+    def write(self, slot: int, image_u8, mask_u8, gt) -> None:
+        """sample `slot` <- (uint8 image (H, W, 3), uint8 class-index mask (H, W), ground truth (G, 5)); slots up to the highest one
+        written count as samples"""
+        slot = int(slot)
+        if not 0 <= slot < self.capacity:
+            raise IndexError(f"resident dataset: slot {slot} outside [0, {self.capacity})")
+        image = np.ascontiguousarray(image_u8, np.uint8)
+        mask = np.ascontiguousarray(mask_u8, np.uint8)
+        if image.shape != (self.height, self.width, 3) or mask.shape != (self.height, self.width):
+            raise ValueError(f"resident dataset: image {image.shape} / mask {mask.shape} for samples of {self.height}x{self.width}")
+        g = np.asarray(gt, np.float32).reshape(-1, 5)
+        if g.shape[0] > self.GMAX:
+            raise ValueError(f"more than {self.GMAX} ground-truth boxes in one image")
+        rows = np.zeros((self.GMAX, 5), np.float32)
+        rows[:g.shape[0]] = g
+        if self.images is None:
+            self._allocate()
+        hw = self.height * self.width
+        self.images.view(slot * hw * 3, image.shape).upload(image)
+        self.masks.view(slot * hw, mask.shape).upload(mask)
+        self.gt.view(slot * self.GMAX * 5, rows.shape).upload(rows)
+        self.cnt.view(slot, (1,)).upload(np.array([g.shape[0]], np.int32))
+        self.num_samples = max(self.num_samples, slot + 1)
+
+    def append(self, image_u8, mask_u8, gt) -> int:
+        slot = self.num_samples
+        self.write(slot, image_u8, mask_u8, gt)
+        return slot
+
+    def __len__(self):
+        """batches per epoch"""
+        n, b = self.num_samples, self.batch_size
+        return n // b if self.drop_remainder else -(-n // b)
+
+    def batch(self, index, flip=None, rgb_draws=None) -> ResidentBatch:
+        """an explicit batch: these samples, mirrored where flagged, with these colour draws"""
+        return ResidentBatch(self, index, flip, rgb_draws)
+
+    def __iter__(self):
+        plan = _epoch_plan(self._rng, self.num_samples, self.batch_size, self.shuffle, bool(self.encoder.augmentation_horizontal_flip),
+                           self.rgb_augmentation, self.drop_remainder)
+        return iter([ResidentBatch(self, index, flip, draws) for index, flip, draws in plan])
+
+    def to_compact(self, batch: ResidentBatch) -> CompactBatch:
+        """the named samples downloaded into an equal CompactBatch (same flips, same draws): for debugging and tests"""
+        hw = self.height * self.width
+        images = np.stack([self.images.view(int(i) * hw * 3, (self.height, self.width, 3)).download() for i in batch.index])
+        masks = np.stack([self.masks.view(int(i) * hw, (self.height, self.width)).download() for i in batch.index])
+        cnt = self.cnt.download()
+        gts = [self.gt.view(int(i) * self.GMAX * 5, (self.GMAX, 5)).download()[:cnt[i]] for i in batch.index]
+        flip = np.zeros(len(batch), np.uint8) if batch.flip is None else batch.flip.copy()
+        return CompactBatch(images, masks, gts, flip, self.encoder, rgb_draws=batch.rgb_draws)
+
+
 def read_image(path_file_image: str) -> np.ndarray:
     """PNG -> float32 (H, W, 3) in 0..255 (reference datacoder.py:468-484)."""
     from PIL import Image

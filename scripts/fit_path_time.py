@@ -2,7 +2,10 @@
 """PCIe-inclusive step time of the full train step as `fit` runs it: every batch handed over as host NumPy arrays
 (images 118 MB, one-hot mask 157 MB, encoded labels/offsets 2 x 4.9 MB at batch 32), versus the resident-input step
 bench.py times; and fit() on compact batches, with and without the device-side colour augmentation.
-usage: python scripts/fit_path_time.py [batch]"""
+usage: python scripts/fit_path_time.py [batch]
+       python scripts/fit_path_time.py [batch] resident    fit() on a device-resident dataset (datacoder.ResidentDataset: per-epoch
+           shuffle and flips drawn on the host, batches gathered from HBM) against fit() on a list of compact batches, alternated,
+           three repeats each, without and with the colour augmentation"""
 import os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "multi-task-learning-object-detection-semantic-segmentation_amd"))
@@ -23,6 +26,44 @@ enc = ssdseglib.datacoder.DataEncoderDecoder(
     iou_threshold=0.525, standard_deviations_centroids_offsets=bench.STDS)
 labels, offsets = enc.encode_batch([gt[i, :cnt[i]] for i in range(batch)])
 y = {'output-mask': mask, 'output-labels': labels, 'output-boxes': offsets}
+
+
+def resident_mode():
+    """images/sec of fit() over K batches: a list of compact batches (39 MB of uint8 up per step, overlapped) vs a ResidentDataset of
+    the same K * batch samples (nothing uploaded); the two alternate so that both see the same clocks"""
+    K, repeats = 10, 3
+    D = ssdseglib.datacoder
+    flags = (np.arange(batch) % 2).astype(np.uint8)
+    gts = [gt[i, :cnt[i]] for i in range(batch)]
+    cb = D.CompactBatch(x.astype(np.uint8), mask.argmax(-1).astype(np.uint8), gts, flags, enc)
+    import copy
+    enc_flip = copy.copy(enc)
+    enc_flip.augmentation_horizontal_flip = True
+    os.environ["SSDSEG_FIT_OVERLAP"] = "1"
+    for colour in (False, True):
+        ds = D.ResidentDataset(enc_flip, capacity=K * batch, batch_size=batch, rgb_augmentation=colour, seed=1993)
+        for k in range(K):
+            for i in range(batch):
+                ds.append(cb.images[i], cb.mask_index[i], gts[i])
+        compact = [D.augmentation_rgb_channels(cb, None)[0] if colour else cb for _ in range(K)]
+        model.fit(compact[:3], epochs=1)
+        model.fit(ds, epochs=1)
+        rates = {"compact": [], "resident": []}
+        for _ in range(repeats):
+            for name, data in (("compact", compact), ("resident", ds)):
+                ctx.sync()
+                t0 = time.perf_counter()
+                model.fit(data, epochs=1)
+                rates[name].append(K * batch / (time.perf_counter() - t0))
+        for name, r in rates.items():
+            print(f"fit() batch {batch}, {K} steps/epoch, {'with' if colour else 'without'} colour augmentation, {name:8s}: "
+                  f"median {np.median(r):.0f} images/sec, repeats {' '.join(f'{v:.0f}' for v in r)} (spread {100 * (max(r) - min(r)) / np.median(r):.1f} %)")
+        del ds
+
+
+if len(sys.argv) > 2 and sys.argv[2] == "resident":
+    resident_mode()
+    sys.exit(0)
 for _ in range(3):
     model.train_on_batch(x, y)
 ctx.sync()
