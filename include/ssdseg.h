@@ -446,6 +446,22 @@ int ssdseg_combined_nms(ssdseg_ctx* ctx, const float* corners, const float* prob
 int ssdseg_seg_suppress(ssdseg_ctx* ctx, const float* mask_prob, int n_pixels_total, int c, const float* probs,
                         int rows, float* probs_out);
 
+/* ---------------------------------------------------------------- test-set evaluation (NB03#cell21-29) on the engine's outputs
+ * jaccard_iou_semantic_segmentation (evaluators.py:189-247) per image and class, without the one-hot mask: prob [n][hw][c] is the
+ *   `output-mask` buffer as the inference engine leaves it, mask_index_u8 [n][hw] the class indices of a compact / resident
+ *   batch; y = (index == class) (an index >= c is an all-zero one-hot pixel, tf.one_hot, as ssdseg_expand_inputs), I = sum y*p,
+ *   T = sum (y + p), iou_out [n][c] = I / (T - I + 1e-7) (evaluators.py:236-241; the mean over the samples is the caller's).
+ *   1 <= c <= 8.  Block partials in the ctx workspace, added in index order in double: the same bits on every run. */
+int ssdseg_eval_mask_jaccard(ssdseg_ctx* ctx, const float* prob, const uint8_t* mask_index_u8, int n, int hw, int c, float* iou_out);
+/* The IoU step of average_precision_object_detection (evaluators.py:6-62 inside :65-186): det [n][r][6] = (label, confidence,
+ *   xmin, ymin, xmax, ymax) as ssdseg_combined_nms writes it, gt [n][gmax][5] = (label, xmin, ymin, xmax, ymax) and gt_count [n]
+ *   as ssdseg_gather_gt / the compact loader hold them; best_out [n][r] = the largest IoU of the prediction with a ground-truth
+ *   box OF THE SAME LABEL -- pixel-inclusive extents (+1), 1e-7 in the denominator, float32, no FMA contraction -- and 0 when the
+ *   image has no ground truth, no label matches, or the prediction's label is 0 (background / an empty NMS row).  The IoU, not a
+ *   true-positive flag: the caller thresholds it once per AP threshold. */
+int ssdseg_eval_det_best_iou(ssdseg_ctx* ctx, const float* det, const float* gt, const int32_t* gt_count, int n, int r, int gmax,
+                             float* best_out);
+
 /* ---------------------------------------------------------------- K20: Adam (Keras 2.13, NB03#cell14)
  * m += (g-m)(1-b1); v += (g^2-v)(1-b2); p -= lr*sqrt(1-b2^t)/(1-b1^t) * m/(sqrt(v)+eps), one flat bucket.
  * grad_scale multiplies g first (1/world_size after the RCCL sum). */

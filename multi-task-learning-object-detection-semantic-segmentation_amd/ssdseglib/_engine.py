@@ -671,19 +671,33 @@ class DecodeNmsOp(Op):
         self.probs_s = ctx.empty((probs.n, a, probs.c)) if suppress_with is not None else None
         self.valid = ctx.empty(boxes.n, np.int32)
         self.name = nms.name
+        self.defer_nms = False      # fwd() stops after decode + suppression; the caller runs run_nms() itself (run_evaluate)
 
-    def fwd(self):
-        b, a, c = self.boxes.n, self.boxes.h * self.boxes.w, self.probs.c
+    def decode(self):
+        """decoded corners and the (segmentation-suppressed) probabilities: everything of the tail that does not depend on the
+        two NMS thresholds"""
+        b, a = self.boxes.n, self.boxes.h * self.boxes.w
         ctx = self.e.ctx
         ctx.call("ssdseg_decode_boxes", self.boxes.buf, self.centroids, b, a, self.stds, self.corners)
-        probs = self.probs.buf
         if self.mask is not None:
             m = self.mask
-            ctx.call("ssdseg_seg_suppress", m.buf, m.m, m.c, probs, b * a, self.probs_s)
-            probs = self.probs_s
+            ctx.call("ssdseg_seg_suppress", m.buf, m.m, m.c, self.probs.buf, b * a, self.probs_s)
+
+    def run_nms(self, boxes_iou_threshold=None, labels_probability_threshold=None, out: Optional[H.DeviceBuffer] = None):
+        """the NMS call alone on what decode() left, with the layer's thresholds or the given ones (a threshold grid re-runs only
+        this: NB03#cell21), into the op's output or `out` [b][max_total][6]"""
+        b, a, c = self.boxes.n, self.boxes.h * self.boxes.w, self.probs.c
         n = self.nms
-        ctx.call("ssdseg_combined_nms", self.corners, probs, b, a, c, n.max_number_of_boxes_per_class, n.max_number_of_boxes_per_sample,
-                 float(n.boxes_iou_threshold), float(n.labels_probability_threshold), self.out.buf, self.valid)
+        iou = n.boxes_iou_threshold if boxes_iou_threshold is None else boxes_iou_threshold
+        prob = n.labels_probability_threshold if labels_probability_threshold is None else labels_probability_threshold
+        probs = self.probs_s if self.mask is not None else self.probs.buf
+        self.e.ctx.call("ssdseg_combined_nms", self.corners, probs, b, a, c, n.max_number_of_boxes_per_class, n.max_number_of_boxes_per_sample,
+                        float(iou), float(prob), self.out.buf if out is None else out, self.valid)
+
+    def fwd(self):
+        self.decode()
+        if not self.defer_nms:
+            self.run_nms()
 
 
 # ====================================================================================================== engine
@@ -1629,6 +1643,98 @@ def run_predict(model: K.Model, data) -> List[np.ndarray]:
     for x, _ in _batches(data):
         chunks.append(run_forward(model, x))
     return [np.concatenate([c[i] for c in chunks], axis=0) for i in range(len(model.outputs))]
+
+
+class _EvalStager:
+    """A test batch (`datacoder.CompactBatch` or `ResidentBatch`, un-augmented) into an inference engine, and the engine's outputs
+    into the numbers of NB03#cell21-29 without leaving the device: the image half of ssdseg_expand_inputs / ssdseg_gather_inputs
+    fills the engine's input; the uint8 class indices go to ssdseg_eval_mask_jaccard as they are (no one-hot target), the
+    ground-truth rows to ssdseg_eval_det_best_iou.  What comes back per batch: iou (n, c), and per NMS threshold pair the
+    detection rows (n, r, 6) and their best IoU (n, r)."""
+
+    GMAX = 64      # ground-truth rows per image, as the compact / resident loaders below
+
+    def __init__(self, eng: "Engine"):
+        self.eng, self.ctx = eng, eng.ctx
+        ctx, b, ins = eng.ctx, eng.batch, eng.input_store
+        v = eng.output_vals[0]
+        if "mask_head" not in v.meta or v.store.ld != v.store.c:
+            raise ValueError("evaluate_on_device needs a model from get_model_for_inference (outputs: mask probabilities, detections)")
+        self.prob = v.store
+        self.nms_op = next((op for op in eng.ops if isinstance(op, DecodeNmsOp)), None)
+        if self.nms_op is None:
+            raise ValueError("evaluate_on_device needs a model from get_model_for_inference (no NMS layer in this one)")
+        self.r = self.nms_op.out.h
+        self.img = ctx.empty((b, ins.h, ins.w, 3), np.uint8)
+        self.midx = ctx.empty((b, ins.h, ins.w), np.uint8)
+        self.gt = ctx.empty((b, self.GMAX, 5))
+        self.cnt = ctx.empty(b, np.int32)
+        self.det = ctx.empty((b, self.r, 6))
+        self.best = ctx.empty((b, self.r))
+        self.iou = ctx.empty((b, self.prob.c))
+
+    def load(self, batch) -> H.DeviceBuffer:
+        """the batch's pixels expanded into the engine's input, its ground truth into gt / cnt -> its class indices [b][hw] on the device"""
+        ctx, b, ins = self.ctx, self.eng.batch, self.eng.input_store
+        if _is_resident(batch):
+            ds = batch.dataset
+            if (ds.height, ds.width) != (ins.h, ins.w):
+                raise ValueError(f"resident batch of {ds.height}x{ds.width} samples for a model of {ins.h}x{ins.w}")
+            if ds.ctx is not ctx or ds.GMAX != self.GMAX:
+                raise ValueError("resident dataset lives on another context than the model's engine")
+            index = batch.index.ctypes.data
+            ctx.call("ssdseg_gather_inputs", ds.images, None, ds.num_samples, index, None, None, None, ins.buf, None, b, ins.h, ins.w, 1)
+            ctx.call("ssdseg_gather_gt", ds.gt, ds.cnt, ds.num_samples, index, None, self.gt, self.cnt, b, self.GMAX, float(ins.w))
+            hw, first = ins.h * ins.w, int(batch.index[0])
+            if np.array_equal(batch.index, np.arange(first, first + b)):
+                return ds.masks.view(first * hw, (b, hw))             # consecutive slots: the pool itself
+            for i, s in enumerate(batch.index):
+                self.midx.view(i * hw, (hw,)).copy_from(ds.masks.view(int(s) * hw, (hw,)))
+            return self.midx
+        if batch.images.shape[1:3] != (ins.h, ins.w):
+            raise ValueError(f"compact batch {batch.images.shape} for a model of {ins.h}x{ins.w}")
+        if max(g.shape[0] for g in batch.ground_truth) > self.GMAX:
+            raise ValueError(f"more than {self.GMAX} ground-truth boxes in one image")
+        gt = np.zeros((b, self.GMAX, 5), np.float32)
+        cnt = np.zeros(b, np.int32)
+        for i, g in enumerate(batch.ground_truth):
+            gt[i, :g.shape[0]] = g
+            cnt[i] = g.shape[0]
+        self.img.upload(batch.images)
+        self.midx.upload(batch.mask_index)
+        self.gt.upload(gt)
+        self.cnt.upload(cnt)
+        ctx.call("ssdseg_expand_inputs", self.img, None, None, ins.buf, None, b, ins.h, ins.w, 1)
+        return self.midx
+
+    def run(self, batch, pairs):
+        """-> iou (n, c) float32, {pair: (detections (n, r, 6), best IoU (n, r))}: one network forward, one decode (+ segmentation
+        suppression), then per threshold pair the NMS and the best-IoU kernel"""
+        eng, ctx, op, b = self.eng, self.ctx, self.nms_op, self.eng.batch
+        midx = self.load(batch)
+        op.defer_nms = True
+        try:
+            eng.forward()
+        finally:
+            op.defer_nms = False
+        ctx.call("ssdseg_eval_mask_jaccard", self.prob.buf, midx, b, self.prob.h * self.prob.w, self.prob.c, self.iou)
+        iou = self.iou.download()
+        out = {}
+        for pair in pairs:
+            op.run_nms(pair[0], pair[1], out=self.det)
+            ctx.call("ssdseg_eval_det_best_iou", self.det, self.gt, self.cnt, b, self.r, self.GMAX, self.best)
+            out[pair] = (self.det.download(), self.best.download())
+        return iou, out
+
+
+def run_evaluate(model: K.Model, batch, pairs):
+    """evaluators.evaluate_on_device's device side for one batch: (iou, {pair: (detections, best IoU)}), see _EvalStager.run.  A
+    batch of another size gets an engine of its own, as in predict."""
+    eng = engine_for(model, len(batch), False)
+    st = eng.__dict__.get("_eval_stager")
+    if st is None:
+        st = eng.__dict__["_eval_stager"] = _EvalStager(eng)
+    return st.run(batch, pairs)
 
 
 def run_train_on_batch(model: K.Model, x, y=None) -> Dict[str, float]:

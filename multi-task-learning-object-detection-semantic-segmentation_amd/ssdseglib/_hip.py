@@ -141,6 +141,8 @@ _SIGNATURES = {
     "ssdseg_decode_boxes": [_vp, _vp, _vp, _i, _i, C.POINTER(_f), _vp],
     "ssdseg_combined_nms": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp],
     "ssdseg_seg_suppress": [_vp, _vp, _i, _i, _vp, _i, _vp],
+    "ssdseg_eval_mask_jaccard": [_vp, _vp, _vp, _i, _i, _i, _vp],
+    "ssdseg_eval_det_best_iou": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "ssdseg_adam_step": [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _f],
     "ssdseg_maxpool3x3s2_fwd": [_vp, _VP, _vp, _i, _i, _i, _i],
     "ssdseg_maxpool3x3s2_bwd": [_vp, _VP, _vp, _vp, _i, _i, _i, _i],

@@ -329,6 +329,7 @@ class ResidentDataset:
         self.num_samples = 0
         self._rng = np.random.default_rng(seed)
         self.ctx = self.images = self.masks = self.gt = self.cnt = None
+        self._gt_labels = {}      # slot -> the labels of its ground-truth rows (int32): what evaluation counts per class on the host
         for sample in samples:
             self.append(*sample[:3])
 
@@ -363,6 +364,7 @@ class ResidentDataset:
         self.masks.view(slot * hw, mask.shape).upload(mask)
         self.gt.view(slot * self.GMAX * 5, rows.shape).upload(rows)
         self.cnt.view(slot, (1,)).upload(np.array([g.shape[0]], np.int32))
+        self._gt_labels[slot] = g[:, 0].astype(np.int32)
         self.num_samples = max(self.num_samples, slot + 1)
 
     def append(self, image_u8, mask_u8, gt) -> int:

@@ -1,16 +1,19 @@
 """Offline evaluation of saved predictions against ground-truth files (reference evaluators.py:6-247).
 
-Host-side NumPy / CSV / PNG post-processing in the reference too -- nothing here is on the GPU hot path.  Same function
-names, arguments and return values:
+Host-side NumPy / CSV / PNG post-processing in the reference too.  Same function names, arguments and return values:
   * `average_precision_object_detection`: per class, predictions of all samples ranked by confidence; a prediction is a true
     positive when its best IoU with a ground-truth box OF THE SAME LABEL reaches the threshold (several predictions may hit the
     same ground-truth box -- the reference does not mark boxes as used); AP = trapezoid area under precision over recall;
   * `jaccard_iou_semantic_segmentation`: the soft Jaccard of the predicted probabilities against one-hot PNG masks, averaged
     over the samples, background dropped from the result.
 IoU conventions as everywhere in the reference: pixel-inclusive extents (+1), 1e-7 in the denominator.
+
+`evaluate_on_device` is both of them for a test set the device already holds (compact or resident batches), over a grid of NMS
+thresholds (NB03#cell21-29): the masks' Jaccard and the predictions' best IoU are reduced on the GPU (csrc/evaluate.hip), only
+the detection rows and a few numbers per image come back, and the ranking tail above runs on them as it does on files.
 """
 import csv
-from typing import Dict, List
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -67,6 +70,13 @@ def average_precision_object_detection(labels_pred_batch, confidences_pred_batch
         best = _iou_boxes_pred_vs_true(lab, box, lt, bt).max(axis=1)
         for l, c, tp in zip(lab, conf, best >= iou_threshold):
             hits[int(l)].append((float(tp), float(c)))
+    return _average_precision_from_hits(hits, n_true, classes)
+
+
+def _average_precision_from_hits(hits, n_true, classes) -> Dict[int, float]:
+    """the ranking and trapezoid tail of reference evaluators.py:65-186, shared by the host and the device path.  hits: per class the
+    (is true positive, confidence) pairs of every prediction of that class, in sample order; n_true: per class the number of
+    ground-truth boxes"""
     out = {}
     for l in classes:
         if n_true[l] == 0 or not hits[l]:
@@ -94,3 +104,101 @@ def jaccard_iou_semantic_segmentation(masks_pred_batch, path_files_masks: List[s
     total = (true + pred).sum(axis=(1, 2))
     iou = (inter / (total - inter + np.float32(_EPS))).mean(axis=0)
     return {l: float(v) for l, v in zip(labels_codes, iou) if l != label_code_background}
+
+
+def _nms_layer(model_inference):
+    for t in model_inference.outputs:
+        if type(t.layer).__name__ == "NonMaximumSuppression":
+            return t.layer
+    raise ValueError("evaluate_on_device needs a model from get_model_for_inference (no NMS output in this one)")
+
+
+def _check_plain(batch) -> None:
+    """evaluation is on the files as they are: no mirrored sample, no colour draws"""
+    kind = type(batch).__name__
+    if kind not in ("CompactBatch", "ResidentBatch"):
+        raise ValueError(f"evaluate_on_device takes CompactBatch / ResidentBatch objects or a ResidentDataset, got {kind}")
+    if getattr(batch, "rgb_draws", None) is not None:
+        raise ValueError("evaluate_on_device: the batch carries colour-augmentation draws")
+    if batch.flip is not None and np.any(batch.flip):
+        raise ValueError("evaluate_on_device: the batch has mirrored samples (flip flags set)")
+
+
+def _plain_batches(data):
+    if type(data).__name__ == "ResidentDataset":
+        # slot order in the dataset's batch size, whatever its shuffle / flip / colour settings; its generator is not consumed
+        n, b = data.num_samples, data.batch_size
+        cuts = [(lo, min(lo + b, n)) for lo in range(0, n, b)]
+        data = [data.batch(np.arange(lo, hi, dtype=np.int32)) for lo, hi in cuts if not (data.drop_remainder and hi - lo < b)]
+    elif isinstance(data, (list, tuple)):
+        for batch in data:                      # a list is checked as a whole before the first batch reaches the device
+            _check_plain(batch)
+    for batch in data:
+        _check_plain(batch)
+        yield batch
+
+
+def _labels_true(batch) -> List[np.ndarray]:
+    """per sample the labels of its ground-truth rows, from the host's copy"""
+    if type(batch).__name__ == "ResidentBatch":
+        return [batch.dataset._gt_labels[int(i)] for i in batch.index]
+    return [g[:, 0].astype(np.int32) for g in batch.ground_truth]
+
+
+def evaluate_on_device(model_inference, data, labels_codes: List[int], label_code_background: int, iou_thresholds: Sequence[float],
+                       nms_grid: Optional[Iterable[Tuple[float, float]]] = None) -> dict:
+    """The test-set evaluation of NB03#cell21-29 on a set the device holds.
+
+    model_inference: from `get_model_for_inference` (suppress_background_boxes=False: with True the detections lose their batch
+    axis, quirk Q7, and belong to no image; use_segmentation_suppression either way).  data: an iterable of
+    `datacoder.CompactBatch`, a `ResidentDataset` (walked in slot order in its batch size, un-augmented, its generator untouched)
+    or an iterable of `ResidentBatch`; no flips, no colour draws.  nms_grid: (boxes_iou_threshold, labels_probability_threshold)
+    pairs, default the model's own.  Per batch the network and the decode (+ segmentation suppression) run once, the NMS once per
+    pair; segmentation suppression is batch-wide (quirk Q6), so the detections are those of `predict` on the same batches.
+
+    -> {'iou': {label: soft Jaccard, mean over the samples (float64, sample order)},
+        'ap': {(b_thr, p_thr): {iou_threshold: {label: average precision}}},
+        'detections': {(b_thr, p_thr): (N, r, 6) rows (label, confidence, xmin, ymin, xmax, ymax)}}
+    without the background in 'iou' and 'ap', as jaccard_iou_semantic_segmentation / average_precision_object_detection, whose
+    values these are (rows of label 0 are empty NMS rows and never count as predictions)."""
+    nms = _nms_layer(model_inference)
+    if nms.suppress_background_boxes:
+        raise ValueError("evaluate_on_device: suppress_background_boxes=True drops the batch axis of the detections (quirk Q7)")
+    labels_codes = list(labels_codes)
+    n_cls = int(model_inference.outputs[0].shape[-1])
+    if len(labels_codes) != n_cls:
+        raise ValueError(f"{len(labels_codes)} label codes for a mask output of {n_cls} classes")
+    pairs = [(float(nms.boxes_iou_threshold), float(nms.labels_probability_threshold))] if nms_grid is None \
+        else [(float(b), float(p)) for b, p in nms_grid]
+    thresholds = [float(t) for t in iou_thresholds]
+    if not pairs or not thresholds:
+        raise ValueError("evaluate_on_device: empty nms_grid or iou_thresholds")
+    classes = [l for l in labels_codes if l != label_code_background]
+    hits = {pair: {t: {l: [] for l in classes} for t in thresholds} for pair in pairs}
+    n_true = {l: 0 for l in classes}
+    detections = {pair: [] for pair in pairs}
+    iou_sum, seen = np.zeros(n_cls, np.float64), 0
+
+    from . import _engine
+    for batch in _plain_batches(data):
+        iou, per_pair = _engine.run_evaluate(model_inference, batch, pairs)
+        for row in iou:
+            iou_sum += row.astype(np.float64)
+            seen += 1
+        for lt in _labels_true(batch):
+            for l in lt:
+                n_true[int(l)] += 1
+        for pair, (det, best) in per_pair.items():
+            detections[pair].append(det)
+            for d, b in zip(det, best):
+                lab = d[:, 0].astype(np.int32)
+                keep = (lab != label_code_background) & (lab != 0)
+                for t in thresholds:
+                    for l, c, tp in zip(lab[keep], d[keep, 1], b[keep] >= t):
+                        hits[pair][t][int(l)].append((float(tp), float(c)))
+    if seen == 0:
+        raise ValueError("evaluate_on_device: no samples")
+    mean = iou_sum / seen
+    return {"iou": {l: float(v) for l, v in zip(labels_codes, mean) if l != label_code_background},
+            "ap": {pair: {t: _average_precision_from_hits(hits[pair][t], n_true, classes) for t in thresholds} for pair in pairs},
+            "detections": {pair: np.concatenate(detections[pair], axis=0) for pair in pairs}}
