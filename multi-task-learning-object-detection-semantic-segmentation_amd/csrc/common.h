@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "ssdseg.h"
@@ -123,6 +124,17 @@ void ssdseg_defer_hold(ssdseg_ctx* ctx, int delta);
     } while (0)
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// Environment switches.  Read on every call, never cached: the parity tests flip them inside one process.
+// env_is: the variable is set and starts with `ch`;  env_int: its integer value, `fallback` when unset
+static inline bool env_is(const char* name, char ch) {
+    const char* e = getenv(name);
+    return e != nullptr && e[0] == ch;
+}
+static inline long long env_int(const char* name, long long fallback) {
+    const char* e = getenv(name);
+    return e != nullptr ? atoll(e) : fallback;
+}
 
 // TF "SAME" geometry
 static inline void same_pad(int in, int k, int s, int d, int* out, int* before) {

@@ -15,13 +15,7 @@
 // The next tile's global loads are issued before the current tile's MFMAs (register prefetch).
 #include "gemm_internal.h"
 
-#include <stdlib.h>
-
 namespace {
-
-constexpr int BM = 128;
-constexpr int BK = 32;
-constexpr int AS = BK + 4;
 
 // (the kernels take these unit-local types, so that their symbols spell the argument type inside the unnamed namespace)
 struct RowAArgs : ssdseg_rowa_args {};
@@ -42,9 +36,8 @@ struct RowAArgs : ssdseg_rowa_args {};
 // schedule), which is what the short-M late layers want: they are latency- not occupancy-bound (too few blocks to fill the
 // chip twice anyway) and ran 10-25 % SLOWER with the tight allocation.  Dispatch: rows >= ROWA_OCC_ROWS.
 constexpr int rowa_min_waves(int WN, int MODE, int NT) { return NT > 0 ? 2 : (WN >= 2 ? 2 : (MODE == 0 ? 4 : 3)); }
-constexpr int ROWA_OCC_ROWS = 150000;
-// (read on every call, like the other dispatch switches: the parity tests flip it between calls to force either instantiation)
-inline long long occ_rows() { const char* e = getenv("SSDSEG_OCC_ROWS"); return e != nullptr ? atoll(e) : ROWA_OCC_ROWS; }
+// (SSDSEG_OCC_ROWS: the parity tests flip it between calls to force either instantiation)
+inline long long occ_rows() { return env_int("SSDSEG_OCC_ROWS", ROWA_OCC_ROWS); }
 template <int WN, int MODE, int LD, int NT = 0, int EP = 0, int OCC = 0>
 __global__ void __launch_bounds__(256, OCC ? rowa_min_waves(WN, MODE, NT) : 1) gemm_rowA_kernel(RowAArgs p) {
     constexpr bool CONV = LD == 1, STEM = LD == 2, FUSEW = NT > 0, F4 = EP >= 1, BNE = EP == 2;
@@ -471,333 +464,6 @@ __global__ void __launch_bounds__(256, OCC ? rowa_min_waves(WN, MODE, NT) : 1) g
     }
 }
 
-// ------------------------------------------------------------------------------------------------ bwd_weight
-struct WGradArgs : ssdseg_wgrad_args {};
-
-// reduction rows per wave per step: 64 rows per block step when the waves split the rows 4- or 2-way, 32 when all four waves
-// sit along k (16-row steps left that shape with two barriers per 8 MFMAs: 2.5-3.2 TB/s of real traffic)
-constexpr int rw_of(int wr) { return wr == 4 ? 16 : 32; }
-
-// WI waves along the output rows (k), WR waves splitting the reduction rows (m); WI*WR == 4.
-// occupancy targets where the raw-load staging would otherwise cost a wave per SIMD (184 registers for <4,1,3>: 2 waves instead of 3)
-constexpr int wgrad_min_waves(int WI, int WR, int WN) { return (WI == 4 && WN <= 2) ? 3 : 1; }
-template <int WI, int WR, int WN>
-__global__ void __launch_bounds__(256, wgrad_min_waves(WI, WR, WN)) gemm_wgrad_kernel(WGradArgs p) {
-    constexpr int RW = rw_of(WR);
-    constexpr int BI = 32 * WI, BJ = 32 * WN, BRT = RW * WR;
-    extern __shared__ float smem[];
-    float* Xs = smem;              // [BRT][BI]
-    float* Ys = smem + BRT * BI;   // [BRT][BJ]
-    const int t = threadIdx.x;
-    const int wave = t >> 6, lane = t & 63, li = lane & 31, hh = lane >> 5;
-    const int wi = wave % WI, wr = wave / WI;
-    const int i0 = blockIdx.y * BI;   // k offset
-    const int j0 = blockIdx.x * BJ;   // n offset
-    const int split = blockIdx.z;
-    const long long mbeg = (long long)split * p.rows_per_split;
-    long long mend = mbeg + p.rows_per_split;
-    if (mend > p.M) mend = p.M;
-    const bool xaff = p.xs != nullptr, gaff = p.gs != nullptr;
-    const float xlo = act_lo(p.xact), xhi = act_hi(p.xact);
-    const float* yptr = gaff ? p.y : p.g;                        // identity gradient view: y aliases g, act NONE
-    const int yact = gaff ? p.gact : SSDSEG_ACT_NONE;
-
-    constexpr int XV = BRT * BI / 4;   // float4 per X tile (== 256 * 2)
-    constexpr int YV = BRT * BJ / 4;
-    constexpr int XQ = (XV + 255) / 256, YQ = (YV + 255) / 256;
-    // Staging in two halves (as in gemm_wres.h): load_tiles() only issues the RAW loads of the next step; store_tiles() -- one
-    // MFMA phase and a barrier later -- applies the views and writes LDS.  With the view arithmetic inside load_tiles every
-    // step waited for its global loads before the first MFMA.  The per-channel view coefficients sit in LDS (loaded once).
-    // (RAW = false: the 96-column tiles of the 30x40 / 15x20 stages, where the extra staging registers cost a wave per SIMD)
-    constexpr bool RAW = !(WI == 4 && WN == 3);
-    float4 xraw[RAW ? XQ : 1], graw[RAW ? YQ : 1], yraw[RAW ? YQ : 1];
-    unsigned xok = 0, yok = 0;   // bit q (stem: bit 4q + element): the slot holds real data
-    float* Xc = smem + BRT * (BI + BJ);   // [2][BI]: scale, shift of the X view
-    float* Yc = Xc + 2 * BI;              // [4][BJ]: scale, shift, k1, k0 of the gradient view
-    for (int i = t; i < BI; i += 256) {
-        const int k = i0 + i;
-        const bool ok = xaff && k < p.K;
-        Xc[i] = ok ? p.xs[k] : 1.f;
-        Xc[BI + i] = ok ? p.xt[k] : 0.f;
-    }
-    for (int i = t; i < BJ; i += 256) {
-        const int n = j0 + i;
-        const bool ok = gaff && n < p.N;
-        Yc[i] = ok ? p.gs[n] : 1.f;
-        Yc[BJ + i] = ok ? p.gt[n] : 0.f;
-        Yc[2 * BJ + i] = ok ? p.gk1[n] : 0.f;
-        Yc[3 * BJ + i] = ok ? p.gk0[n] : 0.f;
-    }
-    // (made visible by the first barrier of the main loop)
-
-    auto load_tiles = [&](long long mrow) {
-        xok = yok = 0;
-#pragma unroll
-        for (int q = 0; q < XQ; ++q) {
-            const int idx = t + 256 * q;
-            float4 v = f4(0.f);
-            if (idx < XV) {
-                const int rr = idx / (BI / 4), c4 = idx % (BI / 4);
-                const long long m = mrow + rr;
-                const int k = i0 + c4 * 4;
-                bool ok = m < mend && k < p.K;
-                long long src = m;
-                if (p.stem) {
-                    const long long hw = (long long)p.convH * p.convW;
-                    const long long img = m / hw;
-                    const int rem = (int)(m - img * hw);
-                    const int ho = rem / p.convW, wo = rem - ho * p.convW;
-                    float e[4];
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq) {
-                        const int rq = k + qq, tap = rq / 3, ci = rq - tap * 3, kh = tap / 3, kw = tap - kh * 3;
-                        const int hi = 2 * ho + kh - p.stemPt, wi = 2 * wo + kw - p.stemPl;
-                        const bool okq = m < mend && rq < p.K && hi >= 0 && hi < p.stemH && wi >= 0 && wi < p.stemW;
-                        e[qq] = p.x[okq ? ((img * p.stemH + hi) * p.stemW + wi) * 3 + ci : 0];
-                        xok |= (okq ? 1u : 0u) << (4 * q + qq);
-                    }
-                    xraw[q] = make_float4(e[0], e[1], e[2], e[3]);
-                    continue;
-                }
-                if (p.convH > 0 && ok) {
-                    const long long hw = (long long)p.convH * p.convW;
-                    const long long img = m / hw;
-                    const int rem = (int)(m - img * hw);
-                    const int hy = rem / p.convW + p.dh, wx = rem % p.convW + p.dw;
-                    ok = hy >= 0 && hy < p.convH && wx >= 0 && wx < p.convW;
-                    src = (img * p.convH + hy) * p.convW + wx;
-                }
-                v = ld4(p.x + (ok ? src * p.ldx + k : 0));
-                xok |= (ok ? 1u : 0u) << (p.stem ? 4 * q : q);
-            }
-            xraw[q] = v;
-        }
-#pragma unroll
-        for (int q = 0; q < YQ; ++q) {
-            const int idx = t + 256 * q;
-            float4 g4 = f4(0.f), y4 = f4(0.f);
-            if (idx < YV) {
-                const int rr = idx / (BJ / 4), c4 = idx % (BJ / 4);
-                const long long m = mrow + rr;
-                const int n = j0 + c4 * 4;
-                const bool ok = m < mend && n < p.N;
-                const long long o = ok ? m * p.ldy + n : 0;
-                g4 = ld4(p.g + o);
-                y4 = ld4(yptr + o);
-                yok |= (ok ? 1u : 0u) << q;
-            }
-            graw[q] = g4;
-            yraw[q] = y4;
-        }
-    };
-    auto store_tiles = [&]() {
-#pragma unroll
-        for (int q = 0; q < XQ; ++q) {
-            const int idx = t + 256 * q;
-            if (idx < XV) {
-                const int c4 = idx % (BI / 4);
-                float4 v;
-                if (p.stem) {
-                    v.x = ((xok >> (4 * q + 0)) & 1u) ? fmaf(xraw[q].x, p.stemScale, p.stemOffset) : 0.f;
-                    v.y = ((xok >> (4 * q + 1)) & 1u) ? fmaf(xraw[q].y, p.stemScale, p.stemOffset) : 0.f;
-                    v.z = ((xok >> (4 * q + 2)) & 1u) ? fmaf(xraw[q].z, p.stemScale, p.stemOffset) : 0.f;
-                    v.w = ((xok >> (4 * q + 3)) & 1u) ? fmaf(xraw[q].w, p.stemScale, p.stemOffset) : 0.f;
-                } else {
-                    v = view_affine4(xraw[q], ld4(Xc + c4 * 4), ld4(Xc + BI + c4 * 4), xlo, xhi);
-                    if (!((xok >> q) & 1u)) v = f4(0.f);
-                }
-                st4(Xs + idx * 4, v);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < YQ; ++q) {
-            const int idx = t + 256 * q;
-            if (idx < YV) {
-                const int c4 = idx % (BJ / 4);
-                float4 v = gview_apply4(graw[q], yraw[q], ld4(Yc + c4 * 4), ld4(Yc + BJ + c4 * 4), ld4(Yc + 2 * BJ + c4 * 4),
-                                        ld4(Yc + 3 * BJ + c4 * 4), yact);
-                if (!((yok >> q) & 1u)) v = f4(0.f);
-                st4(Ys + idx * 4, v);
-            }
-        }
-    };
-
-    // ---- the original staging (view arithmetic at load time), kept for the shapes where it measured faster
-    float4 xreg[RAW ? 1 : XQ], yreg[RAW ? 1 : YQ];   // !RAW: transformed at load time
-
-    // per-thread channel coefficients are fixed across steps when the tile width divides 256 float4 columns;
-    // otherwise they are re-read per step (they sit in L1).
-    auto load_tiles_t = [&](long long mrow) {
-#pragma unroll
-        for (int q = 0; q < XQ; ++q) {
-            const int idx = t + 256 * q;
-            float4 v = f4(0.f);
-            if (idx < XV) {
-                const int rr = idx / (BI / 4), c4 = idx % (BI / 4);
-                const long long m = mrow + rr;
-                const int k = i0 + c4 * 4;
-                bool ok = m < mend && k < p.K;
-                long long src = m;
-                if (p.stem) {
-                    const long long hw = (long long)p.convH * p.convW;
-                    const long long img = m / hw;
-                    const int rem = (int)(m - img * hw);
-                    const int ho = rem / p.convW, wo = rem - ho * p.convW;
-                    float e[4];
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq) {
-                        const int rq = k + qq, tap = rq / 3, ci = rq - tap * 3, kh = tap / 3, kw = tap - kh * 3;
-                        const int hi = 2 * ho + kh - p.stemPt, wi = 2 * wo + kw - p.stemPl;
-                        const bool okq = m < mend && rq < p.K && hi >= 0 && hi < p.stemH && wi >= 0 && wi < p.stemW;
-                        const float xv = p.x[okq ? ((img * p.stemH + hi) * p.stemW + wi) * 3 + ci : 0];
-                        e[qq] = okq ? fmaf(xv, p.stemScale, p.stemOffset) : 0.f;
-                    }
-                    xreg[q] = make_float4(e[0], e[1], e[2], e[3]);
-                    continue;
-                }
-                if (p.convH > 0 && ok) {
-                    const long long hw = (long long)p.convH * p.convW;
-                    const long long img = m / hw;
-                    const int rem = (int)(m - img * hw);
-                    const int hy = rem / p.convW + p.dh, wx = rem % p.convW + p.dw;
-                    ok = hy >= 0 && hy < p.convH && wx >= 0 && wx < p.convW;
-                    src = (img * p.convH + hy) * p.convW + wx;
-                }
-                {
-                    const int kk = ok ? k : 0;
-                    float4 s = f4(1.f), sh = f4(0.f);
-                    if (xaff) { s = ld4(p.xs + kk); sh = ld4(p.xt + kk); }
-                    v = view_affine4(ld4(p.x + (ok ? src * p.ldx + k : 0)), s, sh, xlo, xhi);
-                    if (!ok) v = f4(0.f);
-                }
-            }
-            xreg[q] = v;
-        }
-#pragma unroll
-        for (int q = 0; q < YQ; ++q) {
-            const int idx = t + 256 * q;
-            float4 v = f4(0.f);
-            if (idx < YV) {
-                const int rr = idx / (BJ / 4), c4 = idx % (BJ / 4);
-                const long long m = mrow + rr;
-                const int n = j0 + c4 * 4;
-                {
-                    const bool ok = m < mend && n < p.N;
-                    const long long o = ok ? m * p.ldy + n : 0;
-                    const int nn = ok ? n : 0;
-                    float4 gs = f4(1.f), gt = f4(0.f), gk1 = f4(0.f), gk0 = f4(0.f);
-                    if (gaff) { gs = ld4(p.gs + nn); gt = ld4(p.gt + nn); gk1 = ld4(p.gk1 + nn); gk0 = ld4(p.gk0 + nn); }
-                    v = gview_apply4(ld4(p.g + o), ld4(yptr + o), gs, gt, gk1, gk0, yact);
-                    if (!ok) v = f4(0.f);
-                }
-            }
-            yreg[q] = v;
-        }
-    };
-    auto store_tiles_t = [&]() {
-#pragma unroll
-        for (int q = 0; q < XQ; ++q) {
-            const int idx = t + 256 * q;
-            if (idx < XV) st4(Xs + idx * 4, xreg[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < YQ; ++q) {
-            const int idx = t + 256 * q;
-            if (idx < YV) st4(Ys + idx * 4, yreg[q]);
-        }
-    };
-
-
-    f32x16 acc[WN];
-#pragma unroll
-    for (int nt = 0; nt < WN; ++nt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[nt][e] = 0.f;
-
-    if (mbeg < mend) { if (RAW) load_tiles(mbeg); else load_tiles_t(mbeg); }
-    for (long long mrow = mbeg; mrow < mend; mrow += BRT) {
-        __syncthreads();
-        if (RAW) store_tiles(); else store_tiles_t();
-        __syncthreads();
-        if (mrow + BRT < mend) { if (RAW) load_tiles(mrow + BRT); else load_tiles_t(mrow + BRT); }
-        const float* xa = Xs + (wr * RW + hh) * BI + wi * 32 + li;
-        const float* yb = Ys + (wr * RW + hh) * BJ + li;
-        // fragments of step st + 2 are read while the MFMAs of step st run (see gemm_rowA_kernel: no per-MFMA LDS round trip)
-        constexpr int PF = 2, NST = RW / 2;
-        float afr[PF + 1], bfr[PF + 1][WN];
-        auto fetch = [&](int st, int buf) {
-            afr[buf] = xa[(2 * st) * BI];
-#pragma unroll
-            for (int nt = 0; nt < WN; ++nt) bfr[buf][nt] = yb[(2 * st) * BJ + nt * 32];
-        };
-#pragma unroll
-        for (int q = 0; q < PF; ++q) fetch(q, q);
-#pragma unroll
-        for (int st = 0; st < NST; ++st) {
-            if (st + PF < NST) fetch(st + PF, (st + PF) % (PF + 1));
-            __builtin_amdgcn_sched_barrier(0);   // keep those reads in front of this step's MFMAs
-#pragma unroll
-            for (int nt = 0; nt < WN; ++nt) acc[nt] = mfma32(afr[st % (PF + 1)], bfr[st % (PF + 1)][nt], acc[nt]);
-        }
-    }
-
-    // reduce the WR reduction-waves through LDS, then write the split's partial tile
-    float* out = p.part + (long long)split * p.K * p.N;
-    if (WR > 1) {
-        __syncthreads();
-        float* red = smem;  // [WR-1][WI][WN][16][64]
-        if (wr > 0) {
-#pragma unroll
-            for (int nt = 0; nt < WN; ++nt)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) red[((((wr - 1) * WI + wi) * WN + nt) * 16 + e) * 64 + lane] = acc[nt][e];
-        }
-        __syncthreads();
-        if (wr == 0) {
-#pragma unroll
-            for (int q = 1; q < WR; ++q)
-#pragma unroll
-                for (int nt = 0; nt < WN; ++nt)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[nt][e] += red[((((q - 1) * WI + wi) * WN + nt) * 16 + e) * 64 + lane];
-        }
-    }
-    if (wr == 0) {
-#pragma unroll
-        for (int nt = 0; nt < WN; ++nt) {
-            const int n = j0 + nt * 32 + li;
-            if (n < p.N) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int k = i0 + wi * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                    if (k < p.K) out[(long long)k * p.N + n] = acc[nt][e];
-                }
-            }
-        }
-    }
-}
-
-// Column-tile width in 32-col MFMA tiles.  `row_blocks` = how many blocks the launch has per column tile.
-// Among the widths that still give the chip >= 2 blocks per CU, take the one wasting the fewest padded columns (ties ->
-// wider: more reuse of the streamed operand per block); if no width reaches that, take the one with the most blocks
-// (the 15x20 / 8x10 layers have only 75 / 20 row tiles: a 160-wide tile would leave 180 of 256 CUs idle).
-int pick_wn(int n, long long row_blocks) {
-    int best = 1;
-    long long best_pad = -1, best_blocks = -1;
-    bool best_full = false;
-    for (int wn = 1; wn <= 5; ++wn) {
-        const long long tiles = (n + 32 * wn - 1) / (32 * wn);
-        const long long pad = tiles * 32 * wn, blocks = tiles * row_blocks;
-        const bool full = blocks >= 512;
-        bool take;
-        if (best_pad < 0) take = true;
-        else if (full != best_full) take = full;
-        else if (full) take = pad <= best_pad;
-        else take = blocks > best_blocks || (blocks == best_blocks && pad <= best_pad);
-        if (take) { best = wn; best_pad = pad; best_blocks = blocks; best_full = full; }
-    }
-    return best;
-}
 
 int rowA_wn(int rows, int cols);
 // Backward-data GEMMs with a tiny reduction (<= 48 channels: the project convs of blocks 1-3, the decoder's backbone / logits convs)
@@ -806,26 +472,22 @@ int rowA_wn(int rows, int cols);
 // although the narrow operand is read twice (block-2 project conv 379 -> 277 us).  Only for the register-limited big-M instantiations.
 int rowA_wn_bwd(int rows, int cols, int red) {
     const int wn = rowA_wn(rows, cols);
-    const char* e = getenv("SSDSEG_ROWA_BWD_WN");         // (A/B runs) "0": no cap
-    const int cap = e != nullptr ? atoi(e) : 3;
+    const int cap = (int)env_int("SSDSEG_ROWA_BWD_WN", 3);         // (A/B runs) "0": no cap
     return (cap >= 1 && rows >= occ_rows() && red <= 48 && wn > cap) ? cap : wn;
 }
 int rowA_wn(int rows, int cols) {
     const int wn = pick_wn(cols, cdiv(rows, BM));
-    const char* e = getenv("SSDSEG_ROWA_WN_MAX");        // (A/B runs) widest column tile, in 32-column units
-    if (e != nullptr && atoi(e) >= 1 && wn > atoi(e)) return atoi(e);
-    return wn;
+    const int cap = (int)env_int("SSDSEG_ROWA_WN_MAX", 0);        // (A/B runs) widest column tile, in 32-column units
+    return (cap >= 1 && wn > cap) ? cap : wn;
 }
 
 #include "gemm_wres.h"
 #include "pw_tile.h"
-#include "pw_wgrad.h"
 
 // ---- tile GEMM of the pointwise convs (pw_tile.h): shape -> (waves, column tile), launch
 // SSDSEG_PW_TILE: "0" never, "1" every shape the kernel takes, unset: where it measured faster
 int pw_tile_mode() {
-    const char* e = getenv("SSDSEG_PW_TILE");
-    return e == nullptr ? 2 : (e[0] == '0' ? 0 : 1);
+    return getenv("SSDSEG_PW_TILE") == nullptr ? 2 : (env_is("SSDSEG_PW_TILE", '0') ? 0 : 1);
 }
 
 template <int WAVES, int WN, int MODE, int WNW = 1>
@@ -857,7 +519,7 @@ int pwt_launch_inst(ssdseg_ctx* ctx, const PwTArgs& a, dim3 grid, double cost_by
 // FORWARD below 65,536 rows (project convs of the 30x40 / 15x20 stages 0.8, the SSD head and extra-feature-map convs 0.45-0.8) and the
 // plain input gradients of <= 16k rows (expand convs of blocks 14-16: 0.75-0.85, extra feature maps 0.45).
 bool pw_tile_default(int mode, long long rows, int cred, int nout, bool fused_bn, bool accumulate) {
-    const bool pinned = getenv("SSDSEG_PWT_SMALL") != nullptr && getenv("SSDSEG_PWT_SMALL")[0] == '0';
+    const bool pinned = env_is("SSDSEG_PWT_SMALL", '0');
     if (mode == 0) return nout >= 256 || (rows >= 500000 && cred >= 256) || (rows < 65536 && !pinned);
     if (!fused_bn && !accumulate && rows <= 16384 && !pinned) return true;
     return !fused_bn && !accumulate && cred <= 384 && (nout >= 256 || cred >= 256);
@@ -868,6 +530,13 @@ bool pw_tile_takes(long long rows, int lda, int cred, int nout) {
     return cred % 8 == 0 && cred >= 64 && nout % 4 == 0 && rows * (long long)lda * 4 < (1LL << 31) && (long long)nout * cred * 4 < (1LL << 31);
 }
 
+// THE tile-GEMM question, asked by the forward (launch_rowA), by ssdseg_pwconv_wt_floats -- which tells the engine at lowering
+// whether to keep a transposed weight copy for it -- and by the fused BatchNorm input gradient: does the tile kernel run this layer?
+bool pw_tile_wanted(int mode, long long rows, int lda, int cred, int nout, bool fused_bn, bool accumulate_or_residual) {
+    const int sw = pw_tile_mode();
+    return sw != 0 && pw_tile_takes(rows, lda, cred, nout) && (sw == 1 || pw_tile_default(mode, rows, cred, nout, fused_bn, accumulate_or_residual));
+}
+
 // Short-M layers (the 30x40 / 15x20 stages and the extra feature maps: 38,400 / 9,600 / 2,560 ... rows at batch 32): 128-row tiles
 // give 300 / 75 / 20 row tiles for 256 CUs, so the column tile is what makes the blocks.  Measured per layer
 // (profiles/r02_pw_tile_short_m_per_layer.txt; blocks of one or two waves lost everywhere: every block stages its own weight
@@ -875,8 +544,10 @@ bool pw_tile_takes(long long rows, int lda, int cred, int nout) {
 // SSDSEG_PWT_SMALL=<ncols> overrides the width for A/B runs, "0" restores one tile of <= 160 columns.
 constexpr int PWT_SHORT_ROWS = 65536;
 int pwt_short_ncols(int mode, long long rows, int cred, int nout) {
-    const char* e = getenv("SSDSEG_PWT_SMALL");
-    if (e != nullptr) return atoi(e) >= 32 ? atoi(e) : 0;
+    if (getenv("SSDSEG_PWT_SMALL") != nullptr) {
+        const int nc = (int)env_int("SSDSEG_PWT_SMALL", 0);
+        return nc >= 32 ? nc : 0;
+    }
     const int t64 = cdiv(nout, 64);
     const bool pad64 = cdiv((cdiv(nout, t64) + 3) / 4 * 4, 32) * 32 * t64 * 4 > nout * 5;
     if (mode == 0) {
@@ -886,6 +557,18 @@ int pwt_short_ncols(int mode, long long rows, int cred, int nout) {
     }
     if (rows <= 16384) return 32;
     return nout <= 64 ? 64 : (pad64 ? 32 : 64);
+}
+
+// Blocks along y of a tile-GEMM launch that is free to choose == rows of the BatchNorm-backward partial table its caller sizes:
+// one per `block_rows` rows, at most 1024 blocks per launch over the gx column tiles (SSDSEG_PWT_PARTS >= 64, A/B runs: that many).
+// (ssdseg_pwconv_bwd_data_bn sizes by 256-row blocks from 65,536 rows and one column tile; a block walks row tiles
+// blockIdx.y, blockIdx.y + gridDim.y, ..., so any count is valid for the 128-row blocks of the 4 x 2 wave grid as well)
+int pwt_part_rows(long long rows, int block_rows, int gx) {
+    const int mtiles = cdiv(rows, block_rows);
+    const int parts = (int)env_int("SSDSEG_PWT_PARTS", 0);
+    const int cap = (parts >= 64 ? parts : 1024 * gx) / gx;
+    const int gy = mtiles < cap ? mtiles : cap;
+    return gy < 1 ? 1 : gy;
 }
 
 // nparts_y: number of blocks along y == number of partial rows the caller sized its statistics table for (0: free choice)
@@ -898,8 +581,8 @@ int pw_tile_launch(ssdseg_ctx* ctx, PwTArgs a, int nparts_y, double view_bytes) 
     }
     a.ncols = (cdiv(a.nout, ntiles) + 3) / 4 * 4;
     int wn = cdiv(a.ncols, 32);
-    const char* bige = getenv("SSDSEG_PW_TILE_BIG_ROWS");      // (A/B runs) rows from which the eight-wave 256-row blocks are used
-    const bool big = a.M >= (bige != nullptr ? atoll(bige) : 65536);                       // >= 256 row tiles of 256 rows: eight-wave blocks, one per CU
+    // >= 256 row tiles of 256 rows: eight-wave blocks, one per CU  (SSDSEG_PW_TILE_BIG_ROWS, A/B runs: rows from which they are used)
+    const bool big = a.M >= env_int("SSDSEG_PW_TILE_BIG_ROWS", 65536);
     // column tiles of <= 160: four-wave blocks (two blocks per CU), and the input-gradient kernel whatever its size (its gradient
     // view staging and epilogue need ~60 registers more: 6- and 8-tile instantiations spill)
     if ((!big || MODE == 1) && wn > 5) {
@@ -909,17 +592,10 @@ int pw_tile_launch(ssdseg_ctx* ctx, PwTArgs a, int nparts_y, double view_bytes) 
     }
     // input gradient with 161 .. 256 output columns at >= 65,536 rows (the decoder sepconv): a 4 x 2 wave grid over a 128-row block
     // that spans ALL columns -- the two-tensor operand is streamed once, not once per 128-column tile (SSDSEG_PWT_GRID=0: off)
-    const char* ge = getenv("SSDSEG_PWT_GRID");
-    const bool grid42 = MODE == 1 && big && a.nout > 160 && a.nout <= 256 && !(ge != nullptr && ge[0] == '0');
+    const bool grid42 = MODE == 1 && big && a.nout > 160 && a.nout <= 256 && !env_is("SSDSEG_PWT_GRID", '0');
     if (grid42) { a.ncols = (a.nout + 3) / 4 * 4; wn = cdiv(a.ncols, 64); }
     const int gx = cdiv(a.nout, a.ncols);
-    const int bm = grid42 ? 128 : (big ? 256 : 128);
-    const int mtiles = cdiv(a.M, bm);
-    const char* pe = getenv("SSDSEG_PWT_PARTS");       // (A/B runs) blocks of a launch without a caller-sized statistics table
-    const int cap = (pe != nullptr && atoi(pe) >= 64 ? atoi(pe) : 1024 * gx) / gx;
-    int gy = nparts_y > 0 ? nparts_y : (mtiles < cap ? mtiles : cap);
-    if (gy > mtiles && nparts_y == 0) gy = mtiles;
-    if (gy < 1) gy = 1;
+    const int gy = nparts_y > 0 ? nparts_y : pwt_part_rows(a.M, (big && !grid42) ? 256 : 128, gx);
     a.a_bytes = (unsigned)((((long long)a.M - 1) * a.lda + a.cred) * 4);
     a.wt_bytes = (unsigned)((long long)a.nout * a.cred * 4);
     const dim3 grid(gx, gy, 1);
@@ -954,10 +630,7 @@ int pw_tile_launch(ssdseg_ctx* ctx, PwTArgs a, int nparts_y, double view_bytes) 
 // measurements); 2: SSDSEG_WRES_FORCE=1, resident kernels for every shape that fits (the parity tests run that way)
 int wres_mode() {
     // (read on every call, not cached: the parity tests flip these between calls)
-    const int mode = (getenv("SSDSEG_NO_WRES") != nullptr && getenv("SSDSEG_NO_WRES")[0] == '1')
-                                ? 0
-                                : ((getenv("SSDSEG_WRES_FORCE") != nullptr && getenv("SSDSEG_WRES_FORCE")[0] == '1') ? 2 : 1);
-    return mode;
+    return env_is("SSDSEG_NO_WRES", '1') ? 0 : (env_is("SSDSEG_WRES_FORCE", '1') ? 2 : 1);
 }
 bool wres_enabled() { return wres_mode() != 0; }
 
@@ -967,10 +640,10 @@ int rowA_grid_y_wn(int rows, int cols, int wn);
 int rowA_grid_y(int rows, int cols) { return rowA_grid_y_wn(rows, cols, rowA_wn(rows, cols)); }
 int rowA_grid_y_wn(int rows, int cols, int wn) {
     const int ntiles = cdiv(cols, 32 * wn), mtiles = cdiv(rows, BM);
-    const char* pe = getenv("SSDSEG_ROWA_PARTS");      // (A/B runs) cap of row-tile slots x column tiles
+    const int parts = (int)env_int("SSDSEG_ROWA_PARTS", 0);      // (A/B runs) cap of row-tile slots x column tiles
     // two blocks per CU for the 2-5 tile instantiations; the one-tile ones are compiled for four (three) blocks per CU
     // (rowa_min_waves) and want them: the stem conv ran 225 us on 2048 blocks, 316 us on 512
-    const int cap = pe != nullptr && atoi(pe) >= 64 ? atoi(pe) : (wn == 1 ? 1024 : 512);
+    const int cap = parts >= 64 ? parts : (wn == 1 ? 1024 : 512);
     // few tiles (the short-M stages): one row tile per block -- 75 row tiles dealt to 51 blocks is 2 rounds instead of 1
     if ((long long)mtiles * ntiles <= 2 * cap) return mtiles;
     int gy = cap / ntiles;
@@ -980,19 +653,96 @@ int rowA_grid_y_wn(int rows, int cols, int wn) {
     return cdiv(mtiles, per);
 }
 
+// Algorithmic bytes and flops of one rowA / resident launch: read the streamed operand and the weights once, write
+// the output once; the fused dx + dW pass (NT > 0) also reads X and writes dW.  The dense 3x3 conv (LD == 1) streams its input
+// ONCE per 8(d) -- X + Y + W, not the nine-fold im2col operand the implicit GEMM walks (a.R = 9 * channels).  `view_bytes`: the
+// second tensor of a BatchNorm-backward gradient view (raw y next to g) and, with the fused BatchNorm-backward epilogue (EP == 2),
+// the raw input tensor it reads in place of that BN's own reduction pass.
+struct GemmCost { double bytes, flops, view_bytes; };
+template <int MODE, int LD, int NT, int EP>
+GemmCost rowa_cost(const RowAArgs& a) {
+    const double red_once = LD == 1 ? (double)a.convC : (double)a.R;
+    GemmCost c;
+    c.bytes = 4.0 * ((double)a.I * red_once + (NT > 0 ? 2.0 : 1.0) * ((double)a.I * a.J + (double)a.R * a.J));
+    c.flops = (NT > 0 ? 4.0 : 2.0) * a.I * a.R * a.J;
+    c.view_bytes = ((MODE == 1 && a.cs != nullptr) ? 4.0 * a.I * red_once : 0.0) + (EP == 2 ? 4.0 * a.I * a.J : 0.0);
+    return c;
+}
+
+// THE launch of gemm_rowA_kernel.  LDS: the streamed tile + the weight tile, the statistics reduction scratch, and the
+// 64 x (32 WN + 4) transpose slab of the float4 epilogues, whichever is largest.
+template <int WN, int MODE, int LD, int NT, int EP, int OCC>
+int rowa_launch_inst(ssdseg_ctx* ctx, const RowAArgs& a, dim3 grid) {
+    constexpr size_t tile = (size_t)(BM * AS + BK * (32 * WN + 1)) * sizeof(float);
+    constexpr size_t red = (size_t)(4 * 2 * 32 * WN) * sizeof(float);
+    constexpr size_t slab = EP >= 1 ? (size_t)64 * (32 * WN + 4) * sizeof(float) : 0;
+    constexpr size_t lds = tile > red ? (tile > slab ? tile : slab) : (red > slab ? red : slab);
+    const GemmCost c = rowa_cost<MODE, LD, NT, EP>(a);
+    ctx->timing_view_bytes = c.view_bytes;
+    const char* kname = "";
+    if (ctx->timing) {
+        char kbuf[64];
+        snprintf(kbuf, sizeof(kbuf), "gemm_rowA_kernel<%d, %d, %d, %d, %d, %d>", WN, MODE, LD, NT, EP, OCC);   // = the symbol rocprofv3 shows
+        kname = ssdseg_intern(kbuf);
+    }
+    SSDSEG_LAUNCH_NAMED(ctx, kname, c.bytes, c.flops, (gemm_rowA_kernel<WN, MODE, LD, NT, EP, OCC>), grid, dim3(256), lds, a);
+    SSDSEG_LAUNCH_CHECK();
+    return 0;
+}
+// column-tile width wn in [LO, 5], the occupancy-limited instantiation from occ_rows() rows
+template <int MODE, int LD, int EP, int LO>
+int rowa_launch(ssdseg_ctx* ctx, const RowAArgs& a, int wn, dim3 grid) {
+    return for_width_occ<LO, 5>(wn, a.I >= occ_rows(), [&](auto W, auto OCC) {
+        return rowa_launch_inst<decltype(W)::value, MODE, LD, 0, EP, decltype(OCC)::value>(ctx, a, grid);
+    });
+}
+
+// THE launch of gemm_wres_kernel: whole weight slab resident in LDS, barrier-free per-wave streaming (gemm_wres.h)
+template <int WN, int MODE, int NT>
+int wres_launch_inst(ssdseg_ctx* ctx, const RowAArgs& a, dim3 grid) {
+    const GemmCost c = rowa_cost<MODE, 0, NT, 0>(a);
+    ctx->timing_view_bytes = c.view_bytes;
+    const char* kname = "";
+    if (ctx->timing) {
+        char kbuf[64];
+        snprintf(kbuf, sizeof(kbuf), "gemm_wres_kernel<%d, %d, %d>", WN, MODE, NT);
+        kname = ssdseg_intern(kbuf);
+    }
+    SSDSEG_LAUNCH_NAMED(ctx, kname, c.bytes, c.flops, (gemm_wres_kernel<WN, MODE, NT>), grid, dim3(256), wres_lds_bytes(a.R, WN), a);
+    SSDSEG_LAUNCH_CHECK();
+    return 0;
+}
+
+// the gradient view of a backward-data call as the streamed operand
+RowAArgs rowa_from_gview(const ssdseg_gview* dy, int ldy) {
+    RowAArgs a{};
+    a.a0 = dy->g; a.a1 = dy->y; a.cs = dy->scale; a.ct = dy->shift; a.ck1 = dy->k1; a.ck0 = dy->k0; a.act = dy->act; a.lda = ldy;
+    return a;
+}
+
+// the same GEMM as the tile kernel takes it (wt: the forward wants the transposed weights, see launch_rowA)
+template <int MODE>
+PwTArgs pwt_from_rowa(const RowAArgs& a) {
+    PwTArgs t{};
+    t.a0 = a.a0; t.a1 = (MODE == 1 && a.cs != nullptr) ? a.a1 : a.a0;
+    t.cs = a.cs; t.ct = a.ct; t.ck1 = a.ck1; t.ck0 = a.ck0; t.act = a.act; t.lda = a.lda;
+    t.wt = a.b;
+    t.out = a.out; t.ldo = a.ldo; t.residual = a.residual; t.ldr = a.ldr; t.accumulate = a.accumulate;
+    t.stats = a.stats; t.M = a.I; t.cred = a.R; t.nout = a.J;
+    t.bn_y = a.bn_y; t.ldby = a.ldby; t.bn_s = a.bn_s; t.bn_t = a.bn_t; t.bn_mean = a.bn_mean; t.bn_istd = a.bn_istd; t.bn_act = a.bn_act;
+    t.bnpart = a.bnpart;
+    return t;
+}
+
 // wt_pre (forward only, may be nullptr): the weights already transposed to [J][R] by ssdseg_transpose_batch
 template <int MODE, int LD>
-int launch_rowA(ssdseg_ctx* ctx, const RowAArgs& a0, const float* wt_pre = nullptr) {
-    RowAArgs a = a0;
+int launch_rowA(ssdseg_ctx* ctx, const RowAArgs& a, const float* wt_pre = nullptr) {
     int wn = (MODE == 1 && LD == 0) ? rowA_wn_bwd(a.I, a.J, a.R) : rowA_wn(a.I, a.J);
     const int nparts = rowA_grid_y(a.I, a.J);   // BN-statistics partial rows the caller allocated: fixed by (I, J) alone
-    if (LD == 0 && pw_tile_mode() != 0 && pw_tile_takes(a.I, a.lda, a.R, a.J) && !(MODE == 0 && (a.residual != nullptr || a.accumulate != 0)) && (pw_tile_mode() == 1 || pw_tile_default(MODE, a.I, a.R, a.J, false, a.accumulate != 0 || a.residual != nullptr))) {
-        PwTArgs t{};
-        t.a0 = a.a0; t.a1 = (MODE == 1 && a.cs != nullptr) ? a.a1 : a.a0;
-        t.cs = a.cs; t.ct = a.ct; t.ck1 = a.ck1; t.ck0 = a.ck0; t.act = a.act; t.lda = a.lda;
-        t.out = a.out; t.ldo = a.ldo; t.residual = a.residual; t.ldr = a.ldr; t.accumulate = a.accumulate;
-        t.stats = a.stats; t.M = a.I; t.cred = a.R; t.nout = a.J;
-        t.wt = a.b;
+    const bool adds = a.accumulate != 0 || a.residual != nullptr;
+    // (the forward's residual / accumulate go to the rowA kernel whatever the switches say)
+    if (LD == 0 && !(MODE == 0 && adds) && pw_tile_wanted(MODE, a.I, a.lda, a.R, a.J, false, adds)) {
+        PwTArgs t = pwt_from_rowa<MODE>(a);
         if (MODE == 0 && wt_pre != nullptr) {
             t.wt = wt_pre;
         } else if (MODE == 0) {
@@ -1004,7 +754,7 @@ int launch_rowA(ssdseg_ctx* ctx, const RowAArgs& a0, const float* wt_pre = nullp
             if (rc) return rc;
             t.wt = (const float*)ws;
         }
-        return pw_tile_launch<MODE>(ctx, t, a.stats != nullptr ? nparts : 0, (MODE == 1 && a.cs != nullptr) ? 4.0 * a.I * a.R : 0.0);
+        return pw_tile_launch<MODE>(ctx, t, a.stats != nullptr ? nparts : 0, rowa_cost<MODE, 0, 0, 0>(a).view_bytes);
     }
     // Backward-data of the 30x40-stage expand convs (38400 rows = 300 row tiles, 384-576 reduction channels of a TWO-tensor
     // gradient view, 64-96 output columns): the default picks 32-column tiles to have 600-900 blocks, and every column tile
@@ -1016,265 +766,20 @@ int launch_rowA(ssdseg_ctx* ctx, const RowAArgs& a0, const float* wt_pre = nullp
         const int wide = cdiv(a.J, 32), mtiles = cdiv(a.I, BM);
         if (wide > wn && wide <= 3 && mtiles >= 256 && a.I < ROWA_OCC_ROWS) { wn = wide; grid_y = mtiles < 2048 ? mtiles : 2048; }
     }
-    dim3 grid(cdiv(a.J, 32 * wn), grid_y);
-    size_t lds = (size_t)(BM * AS + BK * (32 * wn + 1)) * sizeof(float);
-    size_t red = (size_t)(4 * 2 * 32 * wn) * sizeof(float);
-    if (red > lds) lds = red;
-    // algorithmic: read the streamed operand and the weights once, write the output once.  The dense 3x3 conv
-    // (LD == 1) streams its input ONCE per 8(d) -- X + Y + W, not the nine-fold im2col operand the implicit GEMM walks (a.R =
-    // 9 * channels).  The second tensor of a BatchNorm-backward gradient view (raw y next to g) is reported as `view_bytes`.
-    const double red_once = LD == 1 ? (double)a.convC : (double)a.R;
-    const double cost_bytes = 4.0 * ((double)a.I * red_once + (double)a.I * a.J + (double)a.R * a.J);
-    const double cost_flops = 2.0 * a.I * a.R * a.J;
-    const double view_bytes = (MODE == 1 && a.cs != nullptr) ? 4.0 * a.I * red_once : 0.0;
-    ctx->timing_view_bytes = view_bytes;
-    const bool occ = a.I >= occ_rows();
-    char kbuf[64];
-    // Measured per layer on MI355X (profiles/r01_wres_vs_general_per_layer.txt): the resident kernel wins when every wave
-    // streams several row tiles (>= ~500k rows: the 240x320 and 120x160 stages at batch 32) and loses 10-30 % below that,
-    // where its once-per-block weight load is not amortised; its 5-tile backward variant needs > 256 registers.
-    if (LD == 0 && wres_lds_bytes(a.R, wn) > 0 && (wres_mode() == 2 || (wres_mode() == 1 && a.I >= 500000 && !(MODE == 1 && wn >= 4)))) {
-        // whole weight slab resident in LDS, barrier-free per-wave streaming (gemm_wres.h); same grid, same partial rows
-        const size_t wl = wres_lds_bytes(a.R, wn);
-        snprintf(kbuf, sizeof(kbuf), "gemm_wres_kernel<%d, %d, 0>", wn, MODE);
-        const char* wname = ctx->timing ? ssdseg_intern(kbuf) : "";
-        constexpr int WM = LD == 0 ? MODE : 0;   // (only instantiated for LD == 0)
-        switch (wn) {
-            case 1: SSDSEG_LAUNCH_NAMED(ctx, wname, cost_bytes, cost_flops, (gemm_wres_kernel<1, WM, 0>), grid, dim3(256), wl, a); break;
-            case 2: SSDSEG_LAUNCH_NAMED(ctx, wname, cost_bytes, cost_flops, (gemm_wres_kernel<2, WM, 0>), grid, dim3(256), wl, a); break;
-            case 3: SSDSEG_LAUNCH_NAMED(ctx, wname, cost_bytes, cost_flops, (gemm_wres_kernel<3, WM, 0>), grid, dim3(256), wl, a); break;
-            case 4: SSDSEG_LAUNCH_NAMED(ctx, wname, cost_bytes, cost_flops, (gemm_wres_kernel<4, WM, 0>), grid, dim3(256), wl, a); break;
-            default: SSDSEG_LAUNCH_NAMED(ctx, wname, cost_bytes, cost_flops, (gemm_wres_kernel<5, WM, 0>), grid, dim3(256), wl, a); break;
-        }
-        SSDSEG_LAUNCH_CHECK();
-        return 0;
+    const dim3 grid(cdiv(a.J, 32 * wn), grid_y);
+    if constexpr (LD == 0) {   // (the resident and float4-epilogue kernels exist for the plain pointwise GEMM only)
+        // Measured per layer on MI355X (profiles/r01_wres_vs_general_per_layer.txt): the resident kernel wins when every wave
+        // streams several row tiles (>= ~500k rows: the 240x320 and 120x160 stages at batch 32) and loses 10-30 % below that,
+        // where its once-per-block weight load is not amortised; its 5-tile backward variant needs > 256 registers.
+        // Same grid, same partial rows as the rowA kernel.
+        if (wres_lds_bytes(a.R, wn) > 0 && (wres_mode() == 2 || (wres_mode() == 1 && a.I >= 500000 && !(MODE == 1 && wn >= 4))))
+            return for_width<1, 5>(wn, [&](auto W) { return wres_launch_inst<decltype(W)::value, MODE, 0>(ctx, a, grid); });
+        // wide, 16-byte-aligned outputs leave through the LDS-transposed float4 epilogue (16 B per lane instead of 4)
+        if (wn >= 2 && !env_is("SSDSEG_NO_F4_EPILOGUE", '1') && a.J % 4 == 0 && a.ldo % 4 == 0 && ((uintptr_t)a.out & 15) == 0 &&
+            (a.residual == nullptr || (a.ldr % 4 == 0 && ((uintptr_t)a.residual & 15) == 0)))
+            return rowa_launch<MODE, 0, 1, 2>(ctx, a, wn, grid);
     }
-    // wide, 16-byte-aligned outputs leave through the LDS-transposed float4 epilogue (16 B per lane instead of 4)
-    const char* f4env = getenv("SSDSEG_NO_F4_EPILOGUE");
-    if (LD == 0 && wn >= 2 && !(f4env != nullptr && f4env[0] == '1') && a.J % 4 == 0 && a.ldo % 4 == 0 &&
-        ((uintptr_t)a.out & 15) == 0 && (a.residual == nullptr || (a.ldr % 4 == 0 && ((uintptr_t)a.residual & 15) == 0))) {
-        const size_t cs = (size_t)64 * (32 * wn + 4) * sizeof(float);
-        if (cs > lds) lds = cs;
-        snprintf(kbuf, sizeof(kbuf), "gemm_rowA_kernel<%d, %d, 0, 0, 1, %d>", wn, MODE, (int)occ);
-        const char* fname = ctx->timing ? ssdseg_intern(kbuf) : "";
-        constexpr int FM = LD == 0 ? MODE : 0;   // (only instantiated for LD == 0)
-        switch (wn) {
-            case 2:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, fname, cost_bytes, cost_flops, (gemm_rowA_kernel<2, FM, 0, 0, 1, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, fname, cost_bytes, cost_flops, (gemm_rowA_kernel<2, FM, 0, 0, 1, 0>), grid, dim3(256), lds, a);
-            break;
-            case 3:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, fname, cost_bytes, cost_flops, (gemm_rowA_kernel<3, FM, 0, 0, 1, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, fname, cost_bytes, cost_flops, (gemm_rowA_kernel<3, FM, 0, 0, 1, 0>), grid, dim3(256), lds, a);
-            break;
-            case 4:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, fname, cost_bytes, cost_flops, (gemm_rowA_kernel<4, FM, 0, 0, 1, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, fname, cost_bytes, cost_flops, (gemm_rowA_kernel<4, FM, 0, 0, 1, 0>), grid, dim3(256), lds, a);
-            break;
-            default:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, fname, cost_bytes, cost_flops, (gemm_rowA_kernel<5, FM, 0, 0, 1, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, fname, cost_bytes, cost_flops, (gemm_rowA_kernel<5, FM, 0, 0, 1, 0>), grid, dim3(256), lds, a);
-            break;
-        }
-        SSDSEG_LAUNCH_CHECK();
-        return 0;
-    }
-    snprintf(kbuf, sizeof(kbuf), "gemm_rowA_kernel<%d, %d, %d, 0, 0, %d>", wn, MODE, LD, (int)occ);   // = the symbol rocprofv3 shows
-    const char* kname = ctx->timing ? ssdseg_intern(kbuf) : "";
-    switch (wn) {
-        case 1:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, MODE, LD, 0, 0, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, MODE, LD, 0, 0, 0>), grid, dim3(256), lds, a);
-            break;
-        case 2:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<2, MODE, LD, 0, 0, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<2, MODE, LD, 0, 0, 0>), grid, dim3(256), lds, a);
-            break;
-        case 3:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<3, MODE, LD, 0, 0, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<3, MODE, LD, 0, 0, 0>), grid, dim3(256), lds, a);
-            break;
-        case 4:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<4, MODE, LD, 0, 0, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<4, MODE, LD, 0, 0, 0>), grid, dim3(256), lds, a);
-            break;
-        default:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<5, MODE, LD, 0, 0, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<5, MODE, LD, 0, 0, 0>), grid, dim3(256), lds, a);
-            break;
-    }
-    SSDSEG_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int WI, int WR>
-int launch_wgrad_wn(ssdseg_ctx* ctx, const WGradArgs& a, int wn, dim3 grid) {
-    size_t lds = ((size_t)(rw_of(WR) * WR) * (32 * WI + 32 * wn) + 2 * 32 * WI + 4 * 32 * wn) * sizeof(float);   // tiles + view coefficients
-    size_t red = (size_t)(WR - 1) * WI * wn * 16 * 64 * sizeof(float);
-    if (red > lds) lds = red;
-    const double share = 1.0 / ((double)grid.x * grid.y);   // every (k-tile, n-tile) block column re-reads its operands
-    const double cost_bytes = 4.0 * ((double)a.M * a.K + (double)a.M * a.N + (double)a.K * a.N);   // 8(d): read X, read dY, write dW
-    const double cost_flops = 2.0 * a.M * a.K * a.N;
-    ctx->timing_view_bytes = a.gs != nullptr ? 4.0 * a.M * a.N : 0.0;
-    (void)share;
-    char kbuf[64];
-    snprintf(kbuf, sizeof(kbuf), "gemm_wgrad_kernel<%d, %d, %d>%s", WI, WR, wn, a.convH > 0 ? " [conv3x3 tap]" : "");
-    const char* kname = ctx->timing ? ssdseg_intern(kbuf) : "";
-    switch (wn) {
-        case 1: SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_wgrad_kernel<WI, WR, 1>), grid, dim3(256), lds, a); break;
-        case 2: SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_wgrad_kernel<WI, WR, 2>), grid, dim3(256), lds, a); break;
-        case 3: SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_wgrad_kernel<WI, WR, 3>), grid, dim3(256), lds, a); break;
-        case 4: SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_wgrad_kernel<WI, WR, 4>), grid, dim3(256), lds, a); break;
-        default: SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_wgrad_kernel<WI, WR, 5>), grid, dim3(256), lds, a); break;
-    }
-    SSDSEG_LAUNCH_CHECK();
-    return 0;
-}
-
-// partial slabs of a split weight gradient (splits * K * N floats, written once and read once by the column sum) are kept below this
-// fraction of the layer's operand traffic M * (K + N)  (SSDSEG_WGRAD_SLAB_FRAC, read per call: A/B runs)
-double slab_fraction() {
-    const char* e = getenv("SSDSEG_WGRAD_SLAB_FRAC");
-    const double f = e != nullptr ? atof(e) : 0.5;
-    return f > 0.0 ? f : 0.5;
-}
-
-// ---- pointwise weight gradient, row-naming form (pw_wgrad.h).  SSDSEG_PW_WGRAD=0: gemm_wgrad_kernel for everything.
-template <int JX, int JY, int WK, int WN>
-int pw_wgrad_launch(ssdseg_ctx* ctx, PwWgArgs a, float* dw) {
-    constexpr int G = 8 / (WK * WN), KT = 32 * JX * WK, NT = 32 * JY * WN, MS = pww_ms(KT, NT);
-    const int ktiles = cdiv(a.K, KT), ntiles = cdiv(a.N, NT);
-    const long long steps = ((long long)a.M + MS - 1) / MS;
-    // blocks: two per CU; every split >= 4 steps; partial slabs (splits * K * N, written and re-read) below half the operand traffic
-    long long splits = (2LL * ctx->num_cus + (long long)ktiles * ntiles - 1) / ((long long)ktiles * ntiles);
-    const long long cap_steps = (steps + 3) / 4;
-    const long long cap_traffic = (long long)((double)a.M * (a.K + a.N) * slab_fraction() / ((double)a.K * a.N));
-    if (splits > cap_steps) splits = cap_steps;
-    if (splits > cap_traffic) splits = cap_traffic;
-    if (splits < 1) splits = 1;
-    if (splits > 65535) splits = 65535;
-    const long long sps = (steps + splits - 1) / splits;
-    splits = (steps + sps - 1) / sps;
-    a.rows_per_split = (int)(sps * MS);
-    const long long slabs = splits;
-    const size_t pb = (size_t)slabs * a.K * a.N * sizeof(float);
-    if (pb >= ((size_t)1 << 31)) return -1;
-    float* part = dw;
-    if (slabs > 1) {
-        void* ws;
-        int rc = ssdseg_partials(ctx, pb, &ws);
-        if (rc) return rc;
-        part = (float*)ws;
-    }
-    a.part = part;
-    a.part_bytes = (unsigned)pb;
-    const size_t lds = pww_lds_bytes(KT, NT, G);
-    static bool configured = false;      // (per instantiation) dynamic LDS beyond 64 KiB has to be announced once
-    if (lds > 64 * 1024 && !configured) {
-        SSDSEG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_wgrad_kernel<JX, JY, WK, WN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured = true;
-    }
-    const double cost_bytes = 4.0 * ((double)a.M * a.K + (double)a.M * a.N + (double)a.K * a.N);   // 8(d): read X, read dY, write dW
-    const double cost_flops = 2.0 * a.M * a.K * a.N;
-    ctx->timing_view_bytes = a.gs != nullptr ? 4.0 * a.M * a.N : 0.0;
-    char kbuf[64];
-    snprintf(kbuf, sizeof(kbuf), "pw_wgrad_kernel<%d, %d, %d, %d>", JX, JY, WK, WN);
-    const char* kname = ctx->timing ? ssdseg_intern(kbuf) : "";
-    SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (pw_wgrad_kernel<JX, JY, WK, WN>), dim3(ntiles, ktiles, (unsigned)splits), dim3(512), lds, a);
-    SSDSEG_LAUNCH_CHECK();
-    if (slabs > 1) return ssdseg_colsum(ctx, part, (int)slabs, (long long)a.K * a.N, dw);
-    return 0;
-}
-
-bool pw_wgrad_enabled() {
-    const char* e = getenv("SSDSEG_PW_WGRAD");
-    return !(e != nullptr && e[0] == '0');
-}
-
-// -> 0 launched, < 0 not taken (the caller falls back), > 0 error
-int pw_wgrad_try(ssdseg_ctx* ctx, const WGradArgs& w, float* dw) {
-    if (!pw_wgrad_enabled() || w.stem || w.convH > 0 || w.K % 4 != 0 || w.N % 4 != 0 || w.ldx % 4 != 0 || w.ldy % 4 != 0) return -1;
-    // the pipelined issue() prefetches one step (<= 64 rows) past the end of a split and forms m0 * ld * 4 in 32 bits
-    if (((long long)w.M + 64) * w.ldx * 4 >= (1LL << 31) || ((long long)w.M + 64) * w.ldy * 4 >= (1LL << 31)) return -1;
-    PwWgArgs a{};
-    a.x = w.x; a.xs = w.xs; a.xt = w.xt; a.xact = w.xact; a.ldx = w.ldx;
-    a.g = w.g; a.y = w.y; a.gs = w.gs; a.gt = w.gt; a.gk1 = w.gk1; a.gk0 = w.gk0; a.gact = w.gact; a.ldy = w.ldy;
-    a.M = w.M; a.K = w.K; a.N = w.N;
-    a.x_bytes = (unsigned)((((long long)w.M - 1) * w.ldx + w.K) * 4);
-    a.g_bytes = (unsigned)((((long long)w.M - 1) * w.ldy + w.N) * 4);
-    // tile = (32 JX WK) x (32 JY WN), chosen per layer among the instantiated shapes (K = 160 on a 256-row tile wastes 37 % of the
-    // MFMAs, three 64-row tiles 17 %; a 24 -> 144 layer on 64-column tiles reads x three times)
-    struct Shape { int kt, nt; int (*launch)(ssdseg_ctx*, PwWgArgs, float*); };
-    static const Shape shapes[] = {
-        {256, 128, &pw_wgrad_launch<2, 2, 4, 2>}, {128, 256, &pw_wgrad_launch<2, 2, 2, 4>}, {128, 128, &pw_wgrad_launch<2, 2, 2, 2>},
-        {256, 64, &pw_wgrad_launch<2, 2, 4, 1>},  {64, 128, &pw_wgrad_launch<2, 2, 1, 2>},  {128, 64, &pw_wgrad_launch<2, 2, 2, 1>},
-        {256, 32, &pw_wgrad_launch<4, 1, 2, 1>},  {64, 64, &pw_wgrad_launch<2, 2, 1, 1>},   {32, 128, &pw_wgrad_launch<1, 4, 1, 1>},
-        {128, 32, &pw_wgrad_launch<4, 1, 1, 1>},  {32, 64, &pw_wgrad_launch<1, 2, 1, 1>},   {64, 32, &pw_wgrad_launch<2, 1, 1, 1>},
-        {32, 32, &pw_wgrad_launch<1, 1, 1, 1>}};
-    // estimated time of a shape = max(padded MFMA work at ~110 TFLOP/s, operand traffic at ~4.5 TB/s): every n-tile re-reads the x
-    // columns of its k-tile and vice versa, so small tiles cost traffic and large ones padding
-    const Shape* best = nullptr;
-    double best_t = 0.0;
-    for (const Shape& sh : shapes) {
-        const double tk = cdiv(w.K, sh.kt), tn = cdiv(w.N, sh.nt);
-        const double t_mfma = 2.0 * w.M * (tk * sh.kt) * (tn * sh.nt) / 110e12;
-        const double t_hbm = 4.0 * w.M * ((double)w.K * tn + (double)w.N * tk) / 4.5e12;
-        const double t = t_mfma > t_hbm ? t_mfma : t_hbm;
-        if (best == nullptr || t < best_t * 0.999) { best = &sh; best_t = t; }      // (listed largest first: ties keep the larger tile)
-    }
-    return best->launch(ctx, a, dw);
-}
-
-// picks the tile shape / split count for dw[k][n] = sum_m x[m][k]*dy[m][n], launches, reduces the split partials
-int wgrad_run(ssdseg_ctx* ctx, WGradArgs a, float* dw) {
-    {
-        const int rc = pw_wgrad_try(ctx, a, dw);
-        if (rc >= 0) return rc;
-    }
-    const int m = a.M, k = a.K, n = a.N;
-    const int wi = k <= 32 ? 1 : (k <= 64 ? 2 : 4);
-    const int wr = 4 / wi;
-    const int brt = rw_of(wr) * wr;
-    const int itiles = cdiv(k, 32 * wi);
-    long long steps = ((long long)m + brt - 1) / brt;
-    // split the reduction rows so that (a) the chip is full, (b) every block still does >= 4 steps and (c) the partial
-    // slabs (splits*k*n floats, written then re-read) stay below half of the operand traffic m*(k+n)
-    long long max_splits = (steps + 3) / 4;
-    const long long traffic_cap = (long long)((double)m * (k + n) * slab_fraction() / ((double)k * n));
-    if (max_splits > traffic_cap) max_splits = traffic_cap < 1 ? 1 : traffic_cap;
-    int wn = pick_wn(n, (long long)itiles * max_splits);
-    // the 4-way row-split shape stages 64 x (32*wn) of (g, y) per step: beyond 3 column tiles it needs > 256 VGPRs (1 wave/SIMD)
-    if (wi == 1 && wn > 3) wn = 3;
-    const int jtiles = cdiv(n, 32 * wn);
-    // target blocks per CU: the long-M (HBM-bound) layers want more, shorter splits in flight; the short-M ones fewer, longer
-    // splits (half the partial slabs, prologue / epilogue amortised over more steps)
-    const char* el = getenv("SSDSEG_WGRAD_BPC_LONG");   // (read per call: tests / A-B runs flip them inside one process)
-    const char* es = getenv("SSDSEG_WGRAD_BPC");
-    const long long bpc_long = el != nullptr ? atoll(el) : 4;
-    const long long bpc_short = es != nullptr ? atoll(es) : 2;
-    const long long bpc = m >= ROWA_OCC_ROWS ? bpc_long : bpc_short;
-    long long want = (bpc * ctx->num_cus + (long long)itiles * jtiles - 1) / ((long long)itiles * jtiles);
-    long long splits = want < 1 ? 1 : (want > max_splits ? max_splits : want);
-    if (splits > 65535) splits = 65535;
-    long long steps_per_split = (steps + splits - 1) / splits;
-    splits = (steps + steps_per_split - 1) / steps_per_split;
-    a.rows_per_split = (int)(steps_per_split * brt);
-    float* part = dw;
-    if (splits > 1) {
-        void* ws;
-        int rc = ssdseg_partials(ctx, (size_t)splits * k * n * sizeof(float), &ws);
-        if (rc) return rc;
-        part = (float*)ws;
-    }
-    a.part = part;
-    dim3 grid(jtiles, itiles, (unsigned)splits);
-    int rc;
-    if (wi == 1) rc = launch_wgrad_wn<1, 4>(ctx, a, wn, grid);
-    else if (wi == 2) rc = launch_wgrad_wn<2, 2>(ctx, a, wn, grid);
-    else rc = launch_wgrad_wn<4, 1>(ctx, a, wn, grid);
-    if (rc) return rc;
-    if (splits > 1) return ssdseg_colsum(ctx, part, (int)splits, (long long)k * n, dw);
-    return 0;
+    return rowa_launch<MODE, LD, 0, 1>(ctx, a, wn, grid);
 }
 
 // Wt[n][k] = W[k][n] for a whole table of matrices in ONE launch: blockIdx.y = matrix, blockIdx.x strides over its 32x32 tiles.
@@ -1307,12 +812,11 @@ __global__ void __launch_bounds__(256) transpose_batch_kernel(const long long* _
 extern "C" {
 
 // ---- what conv3.hip and stem.hip take from this unit (gemm_internal.h): thin wrappers over the templates, so that every
-// gemm_rowA_kernel / gemm_wgrad_kernel instantiation stays in this unit
+// gemm_rowA_kernel instantiation stays in this unit
 int ssdseg_rowA_grid_y(int rows, int cols) { return rowA_grid_y(rows, cols); }
 int ssdseg_rowA_conv3_fwd(ssdseg_ctx* ctx, const ssdseg_rowa_args& a) { return launch_rowA<0, 1>(ctx, RowAArgs{a}); }
 int ssdseg_rowA_conv3_bwd_data(ssdseg_ctx* ctx, const ssdseg_rowa_args& a) { return launch_rowA<1, 1>(ctx, RowAArgs{a}); }
 int ssdseg_rowA_stem_fwd(ssdseg_ctx* ctx, const ssdseg_rowa_args& a) { return launch_rowA<0, 2>(ctx, RowAArgs{a}); }
-int ssdseg_wgrad_run(ssdseg_ctx* ctx, const ssdseg_wgrad_args& a, float* dw) { return wgrad_run(ctx, WGradArgs{a}, dw); }
 
 int ssdseg_pwconv_parts(int m, int n, int* nparts_host) {
     SSDSEG_ARG(m > 0, 1);
@@ -1351,8 +855,7 @@ int ssdseg_pwconv_wt_floats(int m, int ldx, int k, int n, int* floats_host) {
     SSDSEG_ARG(m > 0, 1);
     SSDSEG_ARG(k > 0 && n > 0, 3);
     SSDSEG_ARG(floats_host != nullptr, 5);
-    const bool tile = pw_tile_mode() != 0 && pw_tile_takes(m, ldx, k, n) && (pw_tile_mode() == 1 || pw_tile_default(0, m, k, n, false, false));
-    *floats_host = tile ? k * n : 0;
+    *floats_host = pw_tile_wanted(0, m, ldx, k, n, false, false) ? k * n : 0;
     return 0;
 }
 
@@ -1380,9 +883,7 @@ int ssdseg_pwconv_bwd_data(ssdseg_ctx* ctx, const ssdseg_gview* dy, int ldy, con
     SSDSEG_ARG(k > 0 && k % 4 == 0, 8);
     SSDSEG_ARG(n > 0 && n % 4 == 0, 9);
     SSDSEG_ARG(residual == nullptr || ldr >= k, 11);
-    RowAArgs a{};
-    a.a0 = dy->g; a.a1 = dy->y; a.cs = dy->scale; a.ct = dy->shift; a.ck1 = dy->k1; a.ck0 = dy->k0; a.act = dy->act;
-    a.lda = ldy;
+    RowAArgs a = rowa_from_gview(dy, ldy);
     a.b = w; a.ldb = n;
     a.out = dx; a.ldo = ldx;
     a.residual = residual; a.ldr = ldr; a.accumulate = accumulate;
@@ -1414,8 +915,8 @@ int ssdseg_pwconv_bwd(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, const ssd
     // loses with a single 32-column chunk, where the per-tile set-up dominates.  Its 16*NT accumulator registers cap the
     // occupancy at 1-2 waves per SIMD, which is why it stops at ~3.4 TB/s.  SSDSEG_PW_FUSED=1 forces it for every shape it
     // supports (k <= 32, n <= 192); the parity tests run both ways.
-    const char* fenv = getenv("SSDSEG_PW_FUSED");   // "1": every supported shape, "0": never, unset: where it measured faster
-    const bool force_fused = fenv != nullptr && fenv[0] == '1', never_fused = fenv != nullptr && fenv[0] == '0';
+    // SSDSEG_PW_FUSED "1": every supported shape, "0": never, unset: where it measured faster
+    const bool force_fused = env_is("SSDSEG_PW_FUSED", '1'), never_fused = env_is("SSDSEG_PW_FUSED", '0');
     const bool fused = !never_fused && k <= 32 && n <= 192 && (force_fused || (n > 32 && m >= 500000));
     if (!fused) {
         // dW is off the critical path (nothing reads it before the optimizer): it runs on the side stream, concurrently with
@@ -1426,17 +927,14 @@ int ssdseg_pwconv_bwd(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, const ssd
         if (rc) return rc;
         return ssdseg_pwconv_bwd_data(ctx, dy, ldy, w, dx, lddx, m, k, n, residual, ldr, accumulate);
     }
-    RowAArgs a{};
-    a.a0 = dy->g; a.a1 = dy->y; a.cs = dy->scale; a.ct = dy->shift; a.ck1 = dy->k1; a.ck0 = dy->k0; a.act = dy->act;
-    a.lda = ldy;
+    RowAArgs a = rowa_from_gview(dy, ldy);
     a.b = w; a.ldb = n;
     a.out = dx; a.ldo = lddx;
     a.residual = residual; a.ldr = ldr; a.accumulate = accumulate;
     a.I = m; a.R = n; a.J = k;
     a.xw = in->x; a.xws = in->scale; a.xwt = in->shift; a.xwact = in->act; a.ldxw = ldx;
     const int mtiles = cdiv(m, BM);
-    const int nt = cdiv(n, 32);
-    const size_t wl = wres_enabled() ? wres_lds_bytes(n, 1) : 0;
+    const int nt = cdiv(n, 32);   // NT > 0: fused dW, one accumulator tile per 32-column chunk of dy
     // two resident blocks per CU (112 + 16*NT registers each); every block walks >= 1 row tile.  (Round 3: three blocks per CU for
     // NT <= 3 -- 168 registers, 12 waves per CU -- left the block-1 expand backward at 0.642 ms: not short of waves in flight.)
     int gy = 2 * ctx->num_cus;
@@ -1446,60 +944,13 @@ int ssdseg_pwconv_bwd(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, const ssd
     if (rc) return rc;
     a.wpart = (float*)ws;
     const dim3 grid(1, gy, 1);
-    const size_t lds = (size_t)(BM * AS + BK * 33) * sizeof(float);
-    const double cost_bytes = 4.0 * ((double)m * n + 2.0 * m * k + 2.0 * k * n);   // 8(d): read dY, read X, write dX, read W, write dW
-    const double cost_flops = 4.0 * m * k * n;
-    ctx->timing_view_bytes = dy->scale != nullptr ? 4.0 * m * n : 0.0;
-    if (wl > 0) {
-        char wbuf[64];
-        snprintf(wbuf, sizeof(wbuf), "gemm_wres_kernel<1, 1, %d>", nt > 6 ? 6 : nt);   // NT > 0: fused dW
-        const char* wname = ctx->timing ? ssdseg_intern(wbuf) : "";
-        switch (nt) {
-            case 1: SSDSEG_LAUNCH_NAMED(ctx, wname, cost_bytes, cost_flops, (gemm_wres_kernel<1, 1, 1>), grid, dim3(256), wl, a); break;
-            case 2: SSDSEG_LAUNCH_NAMED(ctx, wname, cost_bytes, cost_flops, (gemm_wres_kernel<1, 1, 2>), grid, dim3(256), wl, a); break;
-            case 3: SSDSEG_LAUNCH_NAMED(ctx, wname, cost_bytes, cost_flops, (gemm_wres_kernel<1, 1, 3>), grid, dim3(256), wl, a); break;
-            case 4: SSDSEG_LAUNCH_NAMED(ctx, wname, cost_bytes, cost_flops, (gemm_wres_kernel<1, 1, 4>), grid, dim3(256), wl, a); break;
-            case 5: SSDSEG_LAUNCH_NAMED(ctx, wname, cost_bytes, cost_flops, (gemm_wres_kernel<1, 1, 5>), grid, dim3(256), wl, a); break;
-            default: SSDSEG_LAUNCH_NAMED(ctx, wname, cost_bytes, cost_flops, (gemm_wres_kernel<1, 1, 6>), grid, dim3(256), wl, a); break;
-        }
-        SSDSEG_LAUNCH_CHECK();
-        if (gy == 1) {
-            SSDSEG_HIP(hipMemcpyAsync(dw, a.wpart, (size_t)k * n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-            return 0;
-        }
-        return ssdseg_colsum(ctx, a.wpart, gy, (long long)k * n, dw);
-    }
-    const bool occ = a.I >= occ_rows();
-    char fbuf[64];
-    snprintf(fbuf, sizeof(fbuf), "gemm_rowA_kernel<1, 1, 0, %d, 0, %d>", nt > 6 ? 6 : nt, (int)occ);   // NT > 0: fused dW
-    const char* kname = ctx->timing ? ssdseg_intern(fbuf) : "";
-    switch (nt) {
-        case 1:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 1, 0, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 1, 0, 0>), grid, dim3(256), lds, a);
-            break;
-        case 2:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 2, 0, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 2, 0, 0>), grid, dim3(256), lds, a);
-            break;
-        case 3:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 3, 0, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 3, 0, 0>), grid, dim3(256), lds, a);
-            break;
-        case 4:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 4, 0, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 4, 0, 0>), grid, dim3(256), lds, a);
-            break;
-        case 5:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 5, 0, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 5, 0, 0>), grid, dim3(256), lds, a);
-            break;
-        default:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 6, 0, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 6, 0, 0>), grid, dim3(256), lds, a);
-            break;
-    }
-    SSDSEG_LAUNCH_CHECK();
+    if (wres_enabled() && wres_lds_bytes(n, 1) > 0)
+        rc = for_width<1, 6>(nt, [&](auto NT) { return wres_launch_inst<1, 1, decltype(NT)::value>(ctx, a, grid); });
+    else
+        rc = for_width_occ<1, 6>(nt, a.I >= occ_rows(), [&](auto NT, auto OCC) {
+            return rowa_launch_inst<1, 1, 0, decltype(NT)::value, 0, decltype(OCC)::value>(ctx, a, grid);
+        });
+    if (rc) return rc;
     if (gy == 1) {
         SSDSEG_HIP(hipMemcpyAsync(dw, a.wpart, (size_t)k * n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         return 0;
@@ -1507,93 +958,37 @@ int ssdseg_pwconv_bwd(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, const ssd
     return ssdseg_colsum(ctx, a.wpart, gy, (long long)k * n, dw);
 }
 
-// dx + dW of a pointwise conv plus the BatchNorm backward of the layer feeding it (the depthwise BN in front of a project conv):
-// the backward-data kernel's float4 epilogue reduces sum(mask*dx), sum(mask*dx*xhat) while it stores dx.  Only valid when this
-// conv is the ONLY consumer of that BatchNorm's output.  Falls back to the separate reduction pass for unaligned tensors.
-// dx = dy * w^T plus the BatchNormalization backward of the layer that feeds this conv (sums in the GEMM epilogue); shared by
-// ssdseg_pwconv_bwd_bn and the tap-expanded form of the narrow 3x3 conv (ssdseg_conv3x3_bwd_data_bn)
+// dx = dy * w^T plus the BatchNormalization backward of the layer that feeds this conv (the depthwise BN in front of a project
+// conv): the backward-data kernel's float4 epilogue reduces sum(mask*dx), sum(mask*dx*xhat) while it stores dx.  Only valid when
+// this conv is the ONLY consumer of that BatchNorm's output.  Falls back to the separate reduction pass for unaligned tensors.
+// Shared by ssdseg_pwconv_bwd_bn and the tap-expanded form of the narrow 3x3 conv (ssdseg_conv3x3_bwd_data_bn).
 int ssdseg_pwconv_bwd_data_bn(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, const ssdseg_gview* dy, int ldy, const float* w, float* dx,
                               int lddx, int m, int k, int n, const float* in_mean, const float* in_invstd, float* in_dgamma,
                               float* in_dbeta, float* in_k1, float* in_k0) {
     int rc = 0;
     const bool aligned = lddx % 4 == 0 && ((uintptr_t)dx & 15) == 0 && ((uintptr_t)in->x & 15) == 0;
-    const char* benv = getenv("SSDSEG_NO_BN_EPILOGUE");
-    if (!aligned || (benv != nullptr && benv[0] == '1')) {
+    if (!aligned || env_is("SSDSEG_NO_BN_EPILOGUE", '1')) {
         rc = ssdseg_pwconv_bwd_data(ctx, dy, ldy, w, dx, lddx, m, k, n, nullptr, 0, 0);
         if (rc) return rc;
         return ssdseg_bn_bwd_reduce(ctx, dx, lddx, in->x, ldx, m, k, in->scale, in->shift, in_mean, in_invstd, in->act, in_dgamma, in_dbeta,
                                     in_k1, in_k0);
     }
-    if (pw_tile_mode() != 0 && pw_tile_takes(m, ldy, n, k) && (pw_tile_mode() == 1 || pw_tile_default(1, m, n, k, true, false))) {
-        // tile GEMM with the BatchNorm-backward sums taken in its epilogue (pw_tile.h)
-        PwTArgs t{};
-        t.a0 = dy->g; t.a1 = dy->scale != nullptr ? dy->y : dy->g;
-        t.cs = dy->scale; t.ct = dy->shift; t.ck1 = dy->k1; t.ck0 = dy->k0; t.act = dy->act; t.lda = ldy;
-        t.wt = w;
-        t.out = dx; t.ldo = lddx;
-        t.M = m; t.cred = n; t.nout = k;
-        const int mt = cdiv(m, m >= 65536 ? 256 : 128);
-        const char* pe = getenv("SSDSEG_PWT_PARTS");
-        const int capb = pe != nullptr && atoi(pe) >= 64 ? atoi(pe) : 1024;
-        const int gy = mt < capb ? mt : capb;
-        void* ws;
-        rc = ssdseg_workspace(ctx, (size_t)gy * 2 * k * sizeof(float), &ws);
-        if (rc) return rc;
-        t.bn_y = in->x; t.ldby = ldx; t.bn_s = in->scale; t.bn_t = in->shift; t.bn_mean = in_mean; t.bn_istd = in_invstd; t.bn_act = in->act;
-        t.bnpart = (float*)ws;
-        rc = pw_tile_launch<1>(ctx, t, gy, 4.0 * ((dy->scale != nullptr ? (double)m * n : 0.0) + (double)m * k));
-        if (rc) return rc;
-        return ssdseg_bn_bwd_finalize_launch(ctx, t.bnpart, gy, k, (double)m, in->scale, in_mean, in_invstd, in_dgamma, in_dbeta, in_k1, in_k0);
-    }
-    RowAArgs a{};
-    a.a0 = dy->g; a.a1 = dy->y; a.cs = dy->scale; a.ct = dy->shift; a.ck1 = dy->k1; a.ck0 = dy->k0; a.act = dy->act;
-    a.lda = ldy;
+    RowAArgs a = rowa_from_gview(dy, ldy);
     a.b = w; a.ldb = n;
     a.out = dx; a.ldo = lddx;
     a.I = m; a.R = n; a.J = k;
+    a.bn_y = in->x; a.ldby = ldx; a.bn_s = in->scale; a.bn_t = in->shift; a.bn_mean = in_mean; a.bn_istd = in_invstd; a.bn_act = in->act;
+    // the tile GEMM takes the BatchNorm-backward sums in its epilogue as well (pw_tile.h); either kernel writes `nparts` partial rows
+    const bool tile = pw_tile_wanted(1, m, ldy, n, k, true, false);
     const int wn = rowA_wn_bwd(m, k, n);
-    const int nparts = rowA_grid_y_wn(m, k, wn);
+    const int nparts = tile ? pwt_part_rows(m, m >= 65536 ? 256 : 128, 1) : rowA_grid_y_wn(m, k, wn);
     void* ws;
     rc = ssdseg_workspace(ctx, (size_t)nparts * 2 * k * sizeof(float), &ws);
     if (rc) return rc;
-    a.bn_y = in->x; a.ldby = ldx; a.bn_s = in->scale; a.bn_t = in->shift; a.bn_mean = in_mean; a.bn_istd = in_invstd; a.bn_act = in->act;
     a.bnpart = (float*)ws;
-    const dim3 grid(cdiv(k, 32 * wn), nparts, 1);
-    size_t lds = (size_t)(BM * AS + BK * (32 * wn + 1)) * sizeof(float);
-    const size_t cs = (size_t)64 * (32 * wn + 4) * sizeof(float);
-    if (cs > lds) lds = cs;
-    // 8(d): read dY, write dX, read W; the raw input tensor read by the fused BatchNorm-backward epilogue replaces that BN's own
-    // reduction pass and is counted with the gradient view's second tensor as `view_bytes`
-    const double cost_bytes = 4.0 * ((double)m * n + (double)m * k + (double)k * n);
-    const double cost_flops = 2.0 * m * k * n;
-    ctx->timing_view_bytes = 4.0 * ((dy->scale != nullptr ? (double)m * n : 0.0) + (double)m * k);
-    const bool occ = m >= occ_rows();
-    char kbuf[64];
-    snprintf(kbuf, sizeof(kbuf), "gemm_rowA_kernel<%d, 1, 0, 0, 2, %d>", wn, (int)occ);
-    const char* kname = ctx->timing ? ssdseg_intern(kbuf) : "";
-    switch (wn) {
-        case 1:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 0, 2, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<1, 1, 0, 0, 2, 0>), grid, dim3(256), lds, a);
-            break;
-        case 2:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<2, 1, 0, 0, 2, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<2, 1, 0, 0, 2, 0>), grid, dim3(256), lds, a);
-            break;
-        case 3:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<3, 1, 0, 0, 2, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<3, 1, 0, 0, 2, 0>), grid, dim3(256), lds, a);
-            break;
-        case 4:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<4, 1, 0, 0, 2, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<4, 1, 0, 0, 2, 0>), grid, dim3(256), lds, a);
-            break;
-        default:
-            if (occ) SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<5, 1, 0, 0, 2, 1>), grid, dim3(256), lds, a);
-            else SSDSEG_LAUNCH_NAMED(ctx, kname, cost_bytes, cost_flops, (gemm_rowA_kernel<5, 1, 0, 0, 2, 0>), grid, dim3(256), lds, a);
-            break;
-    }
-    SSDSEG_LAUNCH_CHECK();
+    if (tile) rc = pw_tile_launch<1>(ctx, pwt_from_rowa<1>(a), nparts, rowa_cost<1, 0, 0, 2>(a).view_bytes);
+    else rc = rowa_launch<1, 0, 2, 1>(ctx, a, wn, dim3(cdiv(k, 32 * wn), nparts, 1));
+    if (rc) return rc;
     return ssdseg_bn_bwd_finalize_launch(ctx, a.bnpart, nparts, k, (double)m, in->scale, in_mean, in_invstd, in_dgamma, in_dbeta, in_k1, in_k0);
 }
 
@@ -1623,25 +1018,5 @@ int ssdseg_pwconv_bwd_bn(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, const 
     return ssdseg_pwconv_bwd_data_bn(ctx, in, ldx, dy, ldy, w, dx, lddx, m, k, n, in_mean, in_invstd, in_dgamma, in_dbeta, in_k1, in_k0);
 }
 
-int ssdseg_pwconv_bwd_weight(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, const ssdseg_gview* dy, int ldy, float* dw,
-                             int m, int k, int n) {
-    SSDSEG_ARG(ctx != nullptr, 1);
-    SSDSEG_ARG(in != nullptr && in->x != nullptr && ((in->scale == nullptr) == (in->shift == nullptr)), 2);
-    SSDSEG_ARG(ldx >= k && ldx % 4 == 0, 3);
-    SSDSEG_ARG(dy != nullptr && dy->g != nullptr, 4);
-    SSDSEG_ARG(dy->scale == nullptr || (dy->y && dy->shift && dy->k1 && dy->k0), 4);
-    SSDSEG_ARG(ldy >= n && ldy % 4 == 0, 5);
-    SSDSEG_ARG(dw != nullptr, 6);
-    SSDSEG_ARG(m > 0, 7);
-    SSDSEG_ARG(k > 0 && k % 4 == 0, 8);
-    SSDSEG_ARG(n > 0 && n % 4 == 0, 9);
-    WGradArgs a{};
-    a.x = in->x; a.xs = in->scale; a.xt = in->shift; a.xact = in->act; a.ldx = ldx;
-    a.g = dy->g; a.y = dy->y; a.gs = dy->scale; a.gt = dy->shift; a.gk1 = dy->k1; a.gk0 = dy->k0; a.gact = dy->act;
-    a.ldy = ldy;
-    a.M = m; a.K = k; a.N = n;
-    return wgrad_run(ctx, a, dw);
-}
 
 }  // extern "C"
-

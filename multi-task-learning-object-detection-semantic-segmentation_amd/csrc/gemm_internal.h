@@ -1,8 +1,57 @@
-// What the units built on the GEMM kernels (conv3.hip, stem.hip) and gemm.hip share: the argument structs of gemm_rowA_kernel /
-// gemm_wgrad_kernel and the few launch helpers that cross the unit boundary.  Hidden helpers like ssdseg_colsum: exported by the
-// library, not part of include/ssdseg.h.  The kernels are instantiated in gemm.hip alone.
+// What gemm.hip, pw_wgrad.hip and the units built on their kernels (conv3.hip, stem.hip) share: the argument structs of
+// gemm_rowA_kernel / gemm_wgrad_kernel, the tile constants, the column-tile rule and the few launch helpers that cross a unit
+// boundary.  Hidden helpers like ssdseg_colsum: exported by the library, not part of include/ssdseg.h.  gemm_rowA_kernel is
+// instantiated in gemm.hip alone, gemm_wgrad_kernel in pw_wgrad.hip alone.
 #pragma once
 #include "common.h"
+
+#include <type_traits>
+
+// gemm_rowA_kernel / gemm_wres_kernel tile: 128 rows per block, 32 reduction channels per step, staged as [128][32 + 4]
+constexpr int BM = 128;
+constexpr int BK = 32;
+constexpr int AS = BK + 4;
+// rows from which the occupancy-limited gemm_rowA_kernel instantiations run; the weight gradient's "long M" by the same count
+constexpr int ROWA_OCC_ROWS = 150000;
+
+// Column-tile width in 32-col MFMA tiles.  `row_blocks` = how many blocks the launch has per column tile.
+// Among the widths that still give the chip >= 2 blocks per CU, take the one wasting the fewest padded columns (ties ->
+// wider: more reuse of the streamed operand per block); if no width reaches that, take the one with the most blocks
+// (the 15x20 / 8x10 layers have only 75 / 20 row tiles: a 160-wide tile would leave 180 of 256 CUs idle).
+inline int pick_wn(int n, long long row_blocks) {
+    int best = 1;
+    long long best_pad = -1, best_blocks = -1;
+    bool best_full = false;
+    for (int wn = 1; wn <= 5; ++wn) {
+        const long long tiles = (n + 32 * wn - 1) / (32 * wn);
+        const long long pad = tiles * 32 * wn, blocks = tiles * row_blocks;
+        const bool full = blocks >= 512;
+        bool take;
+        if (best_pad < 0) take = true;
+        else if (full != best_full) take = full;
+        else if (full) take = pad <= best_pad;
+        else take = blocks > best_blocks || (blocks == best_blocks && pad <= best_pad);
+        if (take) { best = wn; best_pad = pad; best_blocks = blocks; best_full = full; }
+    }
+    return best;
+}
+
+// ---- run-time tile width (and occupancy flag) -> template arguments.  `f` is a generic lambda over std::integral_constant;
+// widths LO .. HI - 1 name themselves, HI is the catch-all, and only the widths of the range are instantiated:
+//   float4 epilogue 2..5 | plain, resident, BN epilogue, weight gradient 1..5 | fused dx + dW (the width is the chunk count NT) 1..6
+template <int LO, int HI, class F>
+int for_width(int w, F&& f) {
+    if constexpr (LO < HI) {
+        if (w == LO) return f(std::integral_constant<int, LO>{});
+        return for_width<LO + 1, HI>(w, f);
+    } else {
+        return f(std::integral_constant<int, HI>{});
+    }
+}
+template <int LO, int HI, class F>
+int for_width_occ(int w, bool occ, F&& f) {
+    return for_width<LO, HI>(w, [&](auto W) { return occ ? f(W, std::integral_constant<int, 1>{}) : f(W, std::integral_constant<int, 0>{}); });
+}
 
 struct ssdseg_rowa_args {
     const float* a0;   // x (fwd) | g (bwd_data)
@@ -82,8 +131,10 @@ int ssdseg_rowA_grid_y(int rows, int cols);
 int ssdseg_rowA_conv3_fwd(ssdseg_ctx* ctx, const ssdseg_rowa_args& a);
 int ssdseg_rowA_conv3_bwd_data(ssdseg_ctx* ctx, const ssdseg_rowa_args& a);
 int ssdseg_rowA_stem_fwd(ssdseg_ctx* ctx, const ssdseg_rowa_args& a);
+// ---- pw_wgrad.hip
 // picks the tile shape / split count for dw[k][n] = sum_m x[m][k]*dy[m][n], launches, reduces the split partials
 int ssdseg_wgrad_run(ssdseg_ctx* ctx, const ssdseg_wgrad_args& a, float* dw);
+// ---- gemm.hip
 // dx = dy * w^T plus the BatchNormalization backward of the layer that feeds this conv (sums in the GEMM epilogue)
 int ssdseg_pwconv_bwd_data_bn(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, const ssdseg_gview* dy, int ldy, const float* w, float* dx,
                               int lddx, int m, int k, int n, const float* in_mean, const float* in_invstd, float* in_dgamma,

@@ -1,5 +1,5 @@
 // Weight gradient of a pointwise (1x1) convolution:  dW[k][n] = sum_m view(x)[m][k] * gview(g, y)[m][n]   (reference blocks.py: every
-// Conv2D(1x1)) -- included by gemm.hip inside its anonymous namespace, after pw_tile.h.
+// Conv2D(1x1)) -- included by pw_wgrad.hip inside its anonymous namespace.
 //
 // The reduction index m (the pixel) is the STRIDED index of both NHWC operands.  gemm_wgrad_kernel stages [pixel][channel] tiles
 // and reads its MFMA operands from them one float at a time -- two ds_read_b32 and some address arithmetic per MFMA -- and

@@ -63,8 +63,8 @@ def kernels(d, llvm):
             if m:
                 cur = m.group(1)
                 code[cur] = []
-            elif cur is not None:
-                at = re.search(r"//\s*([0-9A-Fa-f]+):", line)      # (the comment column holds the absolute address: used, then dropped)
+            elif cur is not None and line.strip() != "...":      # ("...": a run of zero bytes elided, padding behind the unit's last function)
+                at =re.search(r"//\s*([0-9A-Fa-f]+):", line)      # (the comment column holds the absolute address: used, then dropped)
                 if at is None or int(at.group(1), 16) < end[cur]:
                     code[cur].append(re.sub(r"\s*//.*$", "", line).rstrip())
         for name, md in meta.items():
