@@ -414,6 +414,35 @@ int ssdseg_gather_inputs(ssdseg_ctx* ctx, const uint8_t* pool_images, const uint
 int ssdseg_gather_gt(ssdseg_ctx* ctx, const float* pool_gt, const int32_t* pool_cnt, int n_pool, const int32_t* index_host,
                      const uint8_t* flip_host, float* gt, int32_t* gt_count, int b, int gmax, float image_width);
 
+/* Random crop / zoom-out augmentation on the device (datacoder.random_crop_windows; the reference has none: opt-in), the step in
+ * front of the flip and the colour augmentation.  windows_host [b][4] float32 = (x0, y0, w, h) per output sample, in source-pixel
+ * units (pixel i covers [i, i + 1)); a window may reach outside the image (zoom-out) and the output has the sample's own size.
+ * The source is a pool and a HOST index list ([b] int32, every index in [0, n_src)) or, with index_host == NULL, a plain batch
+ * (output n from source n; b <= n_src).  Indices, windows and fill are validated here and passed to the kernels by value, as in
+ * ssdseg_gather_inputs: no copy, no synchronisation, the caller may overwrite them as soon as the call returns.  Every window
+ * must be finite with 1 <= w <= 16 W, 1 <= h <= 16 H, |x0| <= 16 W, |y0| <= 16 H (else the argument error, nothing is launched).
+ * All arithmetic is float32 in the order of the host spec datacoder._crop_resample / _crop_gt, without FMA contraction: the
+ * results are its bytes.  The outputs are a dense compact batch for ssdseg_expand_inputs / ssdseg_rgb_augment /
+ * ssdseg_flip_gt_boxes / ssdseg_encode_targets and must not overlap the sources.
+ * ssdseg_crop_inputs: src_images u8 [n_src][h][w][3] -> images_u8 [b][h][w][3], bilinear: with sx = w / W, X = (x0 + (ox + 0.5)
+ *   sx) - 0.5, xf = floor(X), ax = X - xf (Y, yf, ay likewise), v = top + (bot - top) ay of top = t00 + (t01 - t00) ax and bot
+ *   = t10 + (t11 - t10) ax, byte = floor(v + 0.5); a tap outside the image is fill_rgb_host[3] (NULL: 0, 0, 0).  src_masks u8
+ *   [n_src][h][w] -> mask_index_u8 [b][h][w], nearest: source pixel (floor(y0 + (oy + 0.5) sy), floor(x0 + (ox + 0.5) sx)),
+ *   fill_class (0..255) outside.  Either source / destination pair may be NULL.  A window (0, 0, W, H) copies the sample.
+ *   Pool offsets are 64-bit; h * w * 3 < 2^31.  flip_host [b] u8 or NULL: the batch's flip flags, which the crop does NOT apply
+ *   but writes to flip_out [b] (device, 0 / 1) as they are -- the `flip` argument of the calls that follow, delivered in the
+ *   kernel arguments like the other host lists (a resident batch has no upload to carry them).
+ * ssdseg_crop_gt: src_gt [n_src][gmax][5] = (label, xmin, ymin, xmax, ymax), src_cnt [n_src] -> gt [b][gmax][5], gt_count [b]:
+ *   a row is kept iff its centre ((xmin + xmax) / 2, (ymin + ymax) / 2) has x0 <= cx < x0 + w and y0 <= cy < y0 + h, and after
+ *   x' = (x - x0) (W / w), y' = (y - y0) (H / h) and the clip to [0, W] / [0, H] both xmax' - xmin' >= 1 and ymax' - ymin' >= 1.
+ *   Kept rows stay in their order (ssdseg_encode_targets is order-sensitive), rows past the new count are zeros, the count may
+ *   be 0.  A window exactly (0, 0, W, H) copies the sample's rows verbatim (no centre test, no clip). */
+int ssdseg_crop_inputs(ssdseg_ctx* ctx, const uint8_t* src_images, const uint8_t* src_masks, int n_src, const int32_t* index_host,
+                       const float* windows_host, const uint8_t* fill_rgb_host, int fill_class, const uint8_t* flip_host, uint8_t* flip_out,
+                       uint8_t* images_u8, uint8_t* mask_index_u8, int b, int h, int w);
+int ssdseg_crop_gt(ssdseg_ctx* ctx, const float* src_gt, const int32_t* src_cnt, int n_src, const int32_t* index_host,
+                   const float* windows_host, float* gt, int32_t* gt_count, int b, int gmax, int h, int w);
+
 /* ---------------------------------------------------------------- training metrics
  * Per-image values of the three metric factories NB03#cell14 passes to compile(metrics=...); Keras averages them.
  * jaccard_iou_segmentation_masks_metric (metrics.py:35-47): SOFT Jaccard, inter = sum t*p, total = sum(t+p) over pixels,

@@ -1676,6 +1676,8 @@ class _EvalStager:
     def load(self, batch) -> H.DeviceBuffer:
         """the batch's pixels expanded into the engine's input, its ground truth into gt / cnt -> its class indices [b][hw] on the device"""
         ctx, b, ins = self.ctx, self.eng.batch, self.eng.input_store
+        if getattr(batch, "crop_windows", None) is not None:
+            raise ValueError("evaluate_on_device: the batch carries crop windows; a test set is not augmented")
         if _is_resident(batch):
             ds = batch.dataset
             if (ds.height, ds.width) != (ins.h, ins.w):
@@ -1810,13 +1812,66 @@ def _encoder_anchors(ctx, encoder, det, mask_op):
     return anchors
 
 
+class _CropStage:
+    """The random-crop step of both loaders (csrc/crop.hip): a batch that carries crop windows is cropped, uint8 -> uint8, into device
+    staging buffers of its own -- pixels, class indices, ground-truth rows, counts: an ordinary compact batch -- and the
+    compact-path calls then run on those.  Crop first, then flip, then colour.  The buffers are allocated on first use."""
+
+    def __init__(self, ctx, b, h, w, gmax):
+        self.ctx, self.b, self.h, self.w, self.gmax = ctx, b, h, w, gmax
+        self.img = ctx.empty((b, h, w, 3), np.uint8)
+        self.midx = ctx.empty((b, h, w), np.uint8)
+        self.flip = ctx.empty(b, np.uint8)
+        self.gt = ctx.empty((b, gmax, 5))
+        self.cnt = ctx.empty(b, np.int32)
+
+    def run(self, src_img, src_midx, src_gt, src_cnt, n_src, index, windows, fill, flip_host):
+        """index: the host int32 list of a resident batch or None (n -> n); flip_host: host uint8 flags to hand on to self.flip, or
+        None.  src_midx / src_gt may be None (a model without that head)."""
+        fill = fill if fill is not None else (0, 0, 0, 0)
+        win = windows.ctypes.data_as(C.POINTER(C.c_float))
+        self.ctx.call("ssdseg_crop_inputs", src_img, src_midx, n_src, None if index is None else index.ctypes.data, win,
+                      (C.c_uint8 * 3)(*fill[:3]), int(fill[3]), None if flip_host is None else flip_host.ctypes.data, self.flip, self.img,
+                      self.midx if src_midx is not None else None, self.b, self.h, self.w)
+        if src_gt is not None:
+            self.ctx.call("ssdseg_crop_gt", src_gt, src_cnt, n_src, None if index is None else index.ctypes.data, win, self.gt, self.cnt,
+                          self.b, self.gmax, self.h, self.w)
+
+
+def _crop_stage(ld) -> _CropStage:
+    if ld.crop is None:
+        ins = ld.eng.input_store
+        ld.crop = _CropStage(ld.ctx, ld.eng.batch, ins.h, ins.w, ld.GMAX)
+    return ld.crop
+
+
+def _expand_compact(ld, img, midx, gt, cnt, flip, draws) -> None:
+    """the compact path on device buffers: float32 image (cast or colour augmentation), one-hot mask, both mirrored where flagged,
+    mirrored boxes, encoded anchors, into the buffers the step reads"""
+    ctx, b, ins, enc = ld.ctx, ld.eng.batch, ld.eng.input_store, ld.enc
+    c = ld.mask_op.y_true.shape[-1] if ld.mask_op is not None else 1
+    if draws is None:
+        ctx.call("ssdseg_expand_inputs", img, midx if ld.mask_op is not None else None, flip, ins.buf,
+                 ld.mask_op.y_true if ld.mask_op is not None else None, b, ins.h, ins.w, c)
+    else:
+        ctx.call("ssdseg_rgb_augment", img, flip, (C.c_float * 4)(*draws), ld.means, ins.buf, b, ins.h, ins.w)
+        if ld.mask_op is not None:
+            ctx.call("ssdseg_expand_inputs", None, midx, flip, None, ld.mask_op.y_true, b, ins.h, ins.w, c)
+    if ld.det is not None:
+        if flip is not None:
+            ctx.call("ssdseg_flip_gt_boxes", gt, cnt, flip, b, ld.GMAX, float(ins.w))
+        ctx.call("ssdseg_encode_targets", ld.anchors, ld.anchors.shape[0], gt, cnt, b, ld.GMAX, enc.num_classes,
+                 float(enc.iou_threshold), (C.c_float * 4)(*enc._stds), ld.det.y_labels, ld.det.y_boxes, None)
+
+
 class _CompactLoader:
     """A `datacoder.CompactBatch` into the engine's input / target buffers (reference datacoder.py:302-347 == csrc/inputs.hip +
     ssdseg_encode_targets).  stage(): 39 MB of uint8 pixels / class indices / ground-truth rows go up on the copy stream (under
     the running step when fit overlaps); consume(): the main stream waits for them and expands -- float32 image, one-hot mask,
     both mirrored where flagged, mirrored boxes, encoded anchors -- straight into the buffers the step reads.  A batch that carries
     colour-augmentation draws (datacoder.augmentation_rgb_channels) gets its image from ssdseg_rgb_augment instead of the plain
-    cast (reference datacoder.py:434-466); the mask and the boxes are the same either way."""
+    cast (reference datacoder.py:434-466); the mask and the boxes are the same either way.  A batch that carries crop windows
+    (datacoder.augmentation_random_crop) is cropped first, on the device, into a second set of compact buffers (_CropStage)."""
 
     GMAX = 64       # ground-truth rows per image the encode kernel holds in LDS (boxes.hip)
 
@@ -1834,6 +1889,7 @@ class _CompactLoader:
         self.anchors = _encoder_anchors(ctx, encoder, self.det, self.mask_op)
         self.staged = None
         self.draws = None
+        self.windows = self.fill = self.crop = None
         self._keep = None
 
     def stage(self, cb) -> None:
@@ -1854,29 +1910,25 @@ class _CompactLoader:
             self.ctx.upload_async(dst, src, after_fence=True)
         self._keep = [src for _, src in pairs]
         self.draws = getattr(cb, "rgb_draws", None)
+        self.windows, self.fill = getattr(cb, "crop_windows", None), getattr(cb, "crop_fill", None)
         self.staged = bool(flip.any())
 
     def consume(self) -> None:
         assert self.staged is not None
-        ctx, b, ins, enc = self.ctx, self.eng.batch, self.eng.input_store, self.enc
+        ctx, b = self.ctx, self.eng.batch
         ctx.upload_join()
         flip = self.flip if self.staged else None
-        c = self.mask_op.y_true.shape[-1] if self.mask_op is not None else 1
-        if self.draws is None:
-            ctx.call("ssdseg_expand_inputs", self.img, self.midx if self.mask_op is not None else None, flip, ins.buf,
-                     self.mask_op.y_true if self.mask_op is not None else None, b, ins.h, ins.w, c)
-        else:
-            ctx.call("ssdseg_rgb_augment", self.img, flip, (C.c_float * 4)(*self.draws), self.means, ins.buf, b, ins.h, ins.w)
-            if self.mask_op is not None:
-                ctx.call("ssdseg_expand_inputs", None, self.midx, flip, None, self.mask_op.y_true, b, ins.h, ins.w, c)
-        if self.det is not None:
-            if flip is not None:
-                ctx.call("ssdseg_flip_gt_boxes", self.gt, self.cnt, flip, b, self.GMAX, float(ins.w))
-            ctx.call("ssdseg_encode_targets", self.anchors, self.anchors.shape[0], self.gt, self.cnt, b, self.GMAX, enc.num_classes,
-                     float(enc.iou_threshold), (C.c_float * 4)(*enc._stds), self.det.y_labels, self.det.y_boxes, None)
+        img, midx, gt, cnt = self.img, self.midx, self.gt, self.cnt
+        if self.windows is not None:                # crop first: uint8 -> uint8 into a second compact batch on the device
+            crop = _crop_stage(self)
+            crop.run(img, midx if self.mask_op is not None else None, gt if self.det is not None else None, cnt, b, None, self.windows,
+                     self.fill, None)
+            img, midx, gt, cnt = crop.img, crop.midx, crop.gt, crop.cnt
+        _expand_compact(self, img, midx, gt, cnt, flip, self.draws)
         ctx.upload_fence()                          # from here on the compact staging buffers may be overwritten
         self.staged = None
         self.draws = None
+        self.windows = self.fill = None
 
 
 def _compact_loader(eng: "Engine", cb) -> _CompactLoader:
@@ -1891,7 +1943,9 @@ class _ResidentLoader:
     the batch is a list of indices, flip flags and colour draws.  stage() keeps the list; consume() builds the batch on the main
     stream -- ssdseg_gather_inputs (expansion or colour augmentation, mirrored where flagged), ssdseg_gather_gt (rows, counts,
     mirrored boxes), ssdseg_encode_targets -- with the bits _CompactLoader gives for `dataset.to_compact(batch)`.  Nothing is
-    uploaded and nothing waits."""
+    uploaded and nothing waits.  A batch that carries crop windows (ResidentDataset(random_crop=...)) is instead cropped from the
+    pools into compact buffers on the device (_CropStage: ssdseg_crop_inputs / ssdseg_crop_gt take the index list, and hand the flip
+    flags on in their kernel arguments), and the compact-path calls of _CompactLoader run on those."""
 
     GMAX = _CompactLoader.GMAX
 
@@ -1905,6 +1959,7 @@ class _ResidentLoader:
         self.means = ctx.empty((b, 3))
         self.anchors = _encoder_anchors(ctx, encoder, self.det, self.mask_op)
         self.staged = None
+        self.crop = None
 
     def stage(self, rb) -> None:
         b, ins, ds = self.eng.batch, self.eng.input_store, rb.dataset
@@ -1918,6 +1973,14 @@ class _ResidentLoader:
         assert self.staged is not None
         rb, ctx, b, ins, enc = self.staged, self.ctx, self.eng.batch, self.eng.input_store, self.enc
         ds = rb.dataset
+        if getattr(rb, "crop_windows", None) is not None:
+            crop = _crop_stage(self)
+            flip_host = rb.flip if rb.flip is not None and rb.flip.any() else None
+            crop.run(ds.images, ds.masks if self.mask_op is not None else None, ds.gt if self.det is not None else None, ds.cnt, ds.num_samples,
+                     rb.index, rb.crop_windows, rb.crop_fill, flip_host)
+            _expand_compact(self, crop.img, crop.midx, crop.gt, crop.cnt, crop.flip if flip_host is not None else None, rb.rgb_draws)
+            self.staged = None
+            return
         index = rb.index.ctypes.data
         flip = rb.flip.ctypes.data if rb.flip is not None and rb.flip.any() else None
         draws = (C.c_float * 4)(*rb.rgb_draws) if rb.rgb_draws is not None else None

@@ -166,9 +166,12 @@ class CompactBatch:
     rows (label, xmin, ymin, xmax, ymax) and flip flags -- 39 MB instead of the 285 MB of float32 tensors at batch 32, 480x640.
     `Model.fit` / `train_on_batch` accept it in place of (images, targets): float conversion, one-hot, mirroring and the anchor
     encoding run on the GPU (ssdseg_expand_inputs, ssdseg_flip_gt_boxes, ssdseg_encode_targets).  `augmentation_rgb_channels(cb,
-    targets)` returns a copy carrying one colour-augmentation draw set (`rgb_draws`), applied on the GPU too (ssdseg_rgb_augment)."""
+    targets)` returns a copy carrying one colour-augmentation draw set (`rgb_draws`), applied on the GPU too (ssdseg_rgb_augment);
+    `augmentation_random_crop(cb, targets)` one carrying a crop window per sample (`crop_windows`, `crop_fill` = (r, g, b,
+    fill_class)), applied on the GPU in front of the flip and the colour step (ssdseg_crop_inputs, ssdseg_crop_gt)."""
 
-    def __init__(self, images_u8, mask_index_u8, ground_truth, flip, encoder: "DataEncoderDecoder", rgb_draws=None):
+    def __init__(self, images_u8, mask_index_u8, ground_truth, flip, encoder: "DataEncoderDecoder", rgb_draws=None, *, crop_windows=None,
+                 crop_fill=None):
         self.images = np.ascontiguousarray(images_u8, np.uint8)
         self.mask_index = np.ascontiguousarray(mask_index_u8, np.uint8)
         if self.images.ndim != 4 or self.images.shape[-1] != 3 or self.mask_index.shape != self.images.shape[:3]:
@@ -181,6 +184,10 @@ class CompactBatch:
         # (hue_delta, saturation_factor, contrast_factor, brightness_delta) of augmentation_rgb_channels, applied on the device
         # (ssdseg_rgb_augment) when the batch is expanded; None: the pixels go in as they are
         self.rgb_draws = _check_rgb_draws(rgb_draws)
+        # one crop window (x0, y0, w, h) per sample and (r, g, b, fill_class) for what lies outside the image, applied on the
+        # device (ssdseg_crop_inputs / ssdseg_crop_gt) BEFORE the flip and the colour step; None: no crop
+        self.crop_windows = _check_crop_windows(crop_windows, self.images.shape[0], self.images.shape[1], self.images.shape[2])
+        self.crop_fill = _check_crop_fill(crop_fill)
 
     def __len__(self):
         return self.images.shape[0]
@@ -198,7 +205,183 @@ def _check_rgb_draws(draws):
     return out
 
 
+def _check_crop_windows(windows, b: int, height: int, width: int):
+    """None, or (b, 4) float32 windows (x0, y0, w, h): finite and inside the range the C-ABI takes (include/ssdseg.h)"""
+    if windows is None:
+        return None
+    try:
+        out = np.ascontiguousarray(windows, np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f"crop_windows must be None or a ({b}, 4) array of numbers, got {windows!r}") from None
+    if out.shape != (b, 4):
+        raise ValueError(f"crop_windows must be None or one (x0, y0, w, h) per sample, shape ({b}, 4), got {out.shape}")
+    if not np.isfinite(out).all():
+        raise ValueError("crop_windows must be finite")
+    mw, mh = np.float32(16 * width), np.float32(16 * height)
+    if not ((out[:, 2] >= 1).all() and (out[:, 2] <= mw).all() and (out[:, 3] >= 1).all() and (out[:, 3] <= mh).all()
+            and (np.abs(out[:, 0]) <= mw).all() and (np.abs(out[:, 1]) <= mh).all()):
+        raise ValueError(f"crop_windows: need 1 <= w <= {16 * width}, 1 <= h <= {16 * height}, |x0| <= {16 * width}, |y0| <= {16 * height}")
+    return out
+
+
+def _check_crop_fill(fill):
+    """None, or (r, g, b, fill_class): four integers in 0..255"""
+    if fill is None:
+        return None
+    try:
+        out = tuple(int(v) for v in fill)
+        exact = all(float(v) == float(o) for v, o in zip(fill, out))
+    except (TypeError, ValueError):
+        raise ValueError(f"crop_fill must be None or four integers (r, g, b, fill_class), got {fill!r}") from None
+    if len(out) != 4 or not exact or not all(0 <= v <= 255 for v in out):
+        raise ValueError(f"crop_fill must be None or four integers in 0..255 (r, g, b, fill_class), got {fill!r}")
+    return out
+
+
+# ---- random crop / zoom-out: the host spec of csrc/crop.hip (what _augment_rgb is for the colour kernels).  Everything is float32,
+# in the order written, one rounding per operation: the device follows it operation for operation and is compared for equality.
+_F = np.float32
+
+
+def _crop_axis(origin, extent, size: int):
+    """centres of the `size` output pixels of one axis in source units, u = origin + (o + 0.5) * (extent / size) -> (u, tap index
+    floor(u - 0.5), its weight complement a = (u - 0.5) - floor(u - 0.5)), all (size,) arrays"""
+    step = _F(extent) / _F(size)
+    u = _F(origin) + (np.arange(size, dtype=np.float32) + _F(0.5)) * step
+    t = u - _F(0.5)
+    f = np.floor(t)
+    return u, f.astype(np.int64), t - f
+
+
+def _crop_resample_float(images_u8, windows, fill=(0, 0, 0)):
+    """the bilinear value v of every output pixel BEFORE rounding to a byte, float32 (B, H, W, 3)"""
+    images = np.asarray(images_u8, np.uint8)
+    b, h, w, _ = images.shape
+    windows = np.asarray(windows, np.float32).reshape(b, 4)
+    fill = np.asarray(fill, np.float32).reshape(3)
+    out = np.empty((b, h, w, 3), np.float32)
+    for n in range(b):
+        x0, y0, ww, wh = windows[n]
+        _, xf, ax = _crop_axis(x0, ww, w)
+        _, yf, ay = _crop_axis(y0, wh, h)
+        src = images[n].astype(np.float32)
+
+        def tap(yy, xx):
+            inside = ((yy >= 0) & (yy < h))[:, None] & ((xx >= 0) & (xx < w))[None, :]
+            t = src[np.clip(yy, 0, h - 1)[:, None], np.clip(xx, 0, w - 1)[None, :]]
+            return np.where(inside[..., None], t, fill)
+
+        t00, t01, t10, t11 = tap(yf, xf), tap(yf, xf + 1), tap(yf + 1, xf), tap(yf + 1, xf + 1)
+        ax3, ay3 = ax[None, :, None], ay[:, None, None]
+        top = t00 + (t01 - t00) * ax3
+        bot = t10 + (t11 - t10) * ax3
+        out[n] = top + (bot - top) * ay3
+    return out
+
+
+def _crop_resample(images_u8, masks_u8, windows, fill=(0, 0, 0), fill_class=0):
+    """(uint8 images (B, H, W, 3) or None, uint8 class indices (B, H, W) or None) seen through one window (x0, y0, w, h) per
+    sample: bilinear pixels with `fill` outside the image, byte = floor(v + 0.5); nearest-neighbour class indices with
+    `fill_class` outside.  -> (images, masks) of the same shapes"""
+    out_img = out_mask = None
+    if images_u8 is not None:
+        v = _crop_resample_float(images_u8, windows, fill)
+        out_img = np.floor(v + _F(0.5)).astype(np.uint8)
+    if masks_u8 is not None:
+        masks = np.asarray(masks_u8, np.uint8)
+        b, h, w = masks.shape
+        windows = np.asarray(windows, np.float32).reshape(b, 4)
+        out_mask = np.empty((b, h, w), np.uint8)
+        for n in range(b):
+            x0, y0, ww, wh = windows[n]
+            ux, _, _ = _crop_axis(x0, ww, w)
+            uy, _, _ = _crop_axis(y0, wh, h)
+            xx, yy = np.floor(ux).astype(np.int64), np.floor(uy).astype(np.int64)
+            inside = ((yy >= 0) & (yy < h))[:, None] & ((xx >= 0) & (xx < w))[None, :]
+            out_mask[n] = np.where(inside, masks[n][np.clip(yy, 0, h - 1)[:, None], np.clip(xx, 0, w - 1)[None, :]], np.uint8(fill_class))
+    return out_img, out_mask
+
+
+def _crop_gt(gt_list, windows, height: int, width: int):
+    """per sample the ground-truth rows (label, xmin, ymin, xmax, ymax) that survive its window, in their order: the centre lies in
+    [x0, x0 + w) x [y0, y0 + h) and, shifted, scaled by (W / w, H / h) and clipped to the image, the box is at least 1 x 1.  A
+    window exactly (0, 0, W, H) returns the rows verbatim.  -> list of (G', 5) float32 arrays"""
+    windows = np.asarray(windows, np.float32).reshape(len(gt_list), 4)
+    W, H = _F(width), _F(height)
+    out = []
+    for g, (x0, y0, ww, wh) in zip(gt_list, windows):
+        g = np.asarray(g, np.float32).reshape(-1, 5)
+        if x0 == 0 and y0 == 0 and ww == W and wh == H:
+            out.append(g.copy())
+            continue
+        kx, ky = W / ww, H / wh
+        cx, cy = (g[:, 1] + g[:, 3]) * _F(0.5), (g[:, 2] + g[:, 4]) * _F(0.5)
+        inside = (x0 <= cx) & (cx < x0 + ww) & (y0 <= cy) & (cy < y0 + wh)
+        xmin, xmax = np.clip((g[:, 1] - x0) * kx, _F(0), W), np.clip((g[:, 3] - x0) * kx, _F(0), W)
+        ymin, ymax = np.clip((g[:, 2] - y0) * ky, _F(0), H), np.clip((g[:, 4] - y0) * ky, _F(0), H)
+        keep = inside & (xmax - xmin >= 1) & (ymax - ymin >= 1)
+        out.append(np.stack([g[:, 0], xmin, ymin, xmax, ymax], axis=1).astype(np.float32)[keep])
+    return out
+
+
+def random_crop_windows(rng, n: int, height: int, width: int, probability: float = 0.5, scale=(0.5, 2.0), aspect=(0.75, 4 / 3)):
+    """n crop windows (x0, y0, w, h), float32 (n, 4), in the manner of the SSD recipe's sampling: with probability 1 - `probability`
+    the identity (0, 0, W, H); otherwise s ~ U(scale), a ~ U(aspect), w = s W sqrt(a), h = s H / sqrt(a) (clamped to the C-ABI's
+    [1, 16 W] / [1, 16 H]), x0 ~ U(min(0, W - w), max(0, W - w)) and y0 likewise: a window smaller than the image lies inside it
+    (zoom-in), a larger one contains it (zoom-out).  No box is looked at: a crop that loses every box is a background sample."""
+    n, W, H = int(n), float(width), float(height)
+    if not 0.0 <= float(probability) <= 1.0:
+        raise ValueError(f"random crop: probability {probability!r} outside [0, 1]")
+    (s_lo, s_hi), (a_lo, a_hi) = (float(v) for v in scale), (float(v) for v in aspect)
+    if not (0.0 < s_lo <= s_hi and 0.0 < a_lo <= a_hi):
+        raise ValueError(f"random crop: scale {scale!r} / aspect {aspect!r} must be positive (low, high) ranges")
+    crop = rng.uniform(0.0, 1.0, n) < float(probability)
+    s, a = rng.uniform(s_lo, s_hi, n), rng.uniform(a_lo, a_hi, n)
+    tx, ty = rng.uniform(0.0, 1.0, n), rng.uniform(0.0, 1.0, n)
+    w = np.clip(s * W * np.sqrt(a), 1.0, 16.0 * W).astype(np.float32)
+    h = np.clip(s * H / np.sqrt(a), 1.0, 16.0 * H).astype(np.float32)
+    # the slack W - w in float32 (so x0 + w stays on the right side of W up to one rounding), the origin a point of [0, slack]
+    dx, dy = _F(W) - w, _F(H) - h
+    x0, y0 = (tx * dx).astype(np.float32), (ty * dy).astype(np.float32)
+    out = np.stack([x0, y0, w, h], axis=1).astype(np.float32)
+    out[~crop] = (0.0, 0.0, W, H)
+    return out
+
+
 _aug_rng = np.random.default_rng(1993)
+_crop_rng = np.random.default_rng(1993)     # augmentation_random_crop's own stream: the colour draws of _aug_rng are not disturbed
+
+
+def _split_crop_options(options: dict):
+    """a random_crop option dict -> (the sampler's keywords, crop_fill)"""
+    kw = dict(options)
+    unknown = set(kw) - {"probability", "scale", "aspect", "fill", "fill_class"}
+    if unknown:
+        raise ValueError(f"random crop: unknown option(s) {sorted(unknown)}")
+    fill, fill_class = kw.pop("fill", (0, 0, 0)), kw.pop("fill_class", 0)
+    try:
+        fill = tuple(fill)
+    except TypeError:
+        raise ValueError(f"random crop: fill must be (r, g, b), got {fill!r}") from None
+    if len(fill) != 3:
+        raise ValueError(f"random crop: fill must be (r, g, b), got {fill!r}")
+    return kw, _check_crop_fill(fill + (fill_class,))
+
+
+def augmentation_random_crop(image_batch, targets_batch=None, **options):
+    """random zoom-in crops / zoom-out expansions for a CompactBatch: returns (a new CompactBatch sharing its arrays, with one freshly
+    drawn window per sample attached, targets_batch), the analogue of augmentation_rgb_channels on a compact batch.  options: the
+    keywords of random_crop_windows plus `fill` (r, g, b) and `fill_class`.  The loader applies the windows on the GPU
+    (ssdseg_crop_inputs, ssdseg_crop_gt) before the flip and the colour step.  Float (images, targets) batches are refused: their
+    anchors are already encoded and cannot be re-cropped."""
+    if not isinstance(image_batch, CompactBatch):
+        raise ValueError("augmentation_random_crop takes a CompactBatch: a float (images, targets) batch holds encoded anchors that "
+                         "cannot be re-cropped")
+    cb = image_batch
+    kw, fill = _split_crop_options(options)
+    windows = random_crop_windows(_crop_rng, len(cb), cb.images.shape[1], cb.images.shape[2], **kw)
+    return CompactBatch(cb.images, cb.mask_index, cb.ground_truth, cb.flip, cb.encoder, rgb_draws=cb.rgb_draws, crop_windows=windows,
+                        crop_fill=fill), targets_batch
 
 
 def _draw_rgb():
@@ -251,7 +434,8 @@ def augmentation_rgb_channels(image_batch, targets_batch):
     draws = _draw_rgb()
     if isinstance(image_batch, CompactBatch):
         cb = image_batch
-        return CompactBatch(cb.images, cb.mask_index, cb.ground_truth, cb.flip, cb.encoder, rgb_draws=draws), targets_batch
+        return CompactBatch(cb.images, cb.mask_index, cb.ground_truth, cb.flip, cb.encoder, rgb_draws=draws, crop_windows=cb.crop_windows,
+                            crop_fill=cb.crop_fill), targets_batch
     return _augment_rgb(image_batch, *draws), targets_batch
 
 
@@ -279,9 +463,10 @@ def _epoch_plan(rng, num_samples: int, batch_size: int, shuffle: bool, flip: boo
 
 class ResidentBatch:
     """A batch of a ResidentDataset: which samples (`index`, int32), which of them mirrored (`flip`, uint8 or None) and the colour
-    draws (`rgb_draws` or None) -- a few host bytes; the pixels stay on the device.  `Model.fit` / `train_on_batch` accept it."""
+    draws (`rgb_draws` or None), and optionally one crop window per sample (`crop_windows`, `crop_fill`, as CompactBatch) -- a few
+    host bytes; the pixels stay on the device.  `Model.fit` / `train_on_batch` accept it."""
 
-    def __init__(self, dataset: "ResidentDataset", index, flip=None, rgb_draws=None):
+    def __init__(self, dataset: "ResidentDataset", index, flip=None, rgb_draws=None, *, crop_windows=None, crop_fill=None):
         self.dataset = dataset
         self.index = np.ascontiguousarray(index, np.int32).reshape(-1)
         if self.index.size == 0:
@@ -292,6 +477,8 @@ class ResidentBatch:
         if self.flip is not None and self.flip.size != self.index.size:
             raise ValueError("resident batch: one flip flag per sample")
         self.rgb_draws = _check_rgb_draws(rgb_draws)
+        self.crop_windows = _check_crop_windows(crop_windows, self.index.size, dataset.height, dataset.width)
+        self.crop_fill = _check_crop_fill(crop_fill)
 
     @property
     def encoder(self):
@@ -310,12 +497,15 @@ class ResidentDataset:
     The batches are `ResidentBatch` objects: `Model.fit(ds, epochs=N)` builds each one on the device (ssdseg_gather_inputs,
     ssdseg_gather_gt, ssdseg_encode_targets), so after the upload no pixel crosses PCIe and the host does no per-sample work.
     `samples`: an iterable of `read_compact` tuples (their flip flag is ignored); `capacity`: slots to allocate (default: the number
-    of samples), filled with `append` / `write` without holding the set on the host."""
+    of samples), filled with `append` / `write` without holding the set on the host.
+    `random_crop`: None (the chain above, nothing else drawn), or a dict of random_crop_windows' keywords plus optional `fill` (r, g,
+    b) / `fill_class`: every batch then carries one crop window per sample, drawn from the same Generator AFTER the epoch's
+    permutation, flips and colour draws, and the device crops before it flips and colours (ssdseg_crop_inputs, ssdseg_crop_gt)."""
 
     GMAX = 64       # ground-truth rows per sample, as the compact loader (the encode kernel holds them in LDS)
 
     def __init__(self, encoder: "DataEncoderDecoder", samples=None, *, capacity: Optional[int] = None, batch_size: int = 16,
-                 shuffle: bool = True, rgb_augmentation: bool = False, drop_remainder: bool = False, seed=None):
+                 shuffle: bool = True, rgb_augmentation: bool = False, drop_remainder: bool = False, seed=None, random_crop=None):
         samples = list(samples) if samples is not None else []
         capacity = len(samples) if capacity is None else int(capacity)
         if capacity <= 0 or capacity < len(samples):
@@ -326,6 +516,10 @@ class ResidentDataset:
         self.capacity, self.batch_size = capacity, int(batch_size)
         self.shuffle, self.rgb_augmentation, self.drop_remainder = bool(shuffle), bool(rgb_augmentation), bool(drop_remainder)
         self.height, self.width = int(encoder.image_height), int(encoder.image_width)
+        self.random_crop = None
+        if random_crop is not None:
+            self.random_crop = _split_crop_options(random_crop)
+            random_crop_windows(np.random.default_rng(0), 1, self.height, self.width, **self.random_crop[0])      # bad options fail here
         self.num_samples = 0
         self._rng = np.random.default_rng(seed)
         self.ctx = self.images = self.masks = self.gt = self.cnt = None
@@ -377,24 +571,29 @@ class ResidentDataset:
         n, b = self.num_samples, self.batch_size
         return n // b if self.drop_remainder else -(-n // b)
 
-    def batch(self, index, flip=None, rgb_draws=None) -> ResidentBatch:
-        """an explicit batch: these samples, mirrored where flagged, with these colour draws"""
-        return ResidentBatch(self, index, flip, rgb_draws)
+    def batch(self, index, flip=None, rgb_draws=None, *, crop_windows=None, crop_fill=None) -> ResidentBatch:
+        """an explicit batch: these samples, seen through these crop windows, mirrored where flagged, with these colour draws"""
+        return ResidentBatch(self, index, flip, rgb_draws, crop_windows=crop_windows, crop_fill=crop_fill)
 
     def __iter__(self):
         plan = _epoch_plan(self._rng, self.num_samples, self.batch_size, self.shuffle, bool(self.encoder.augmentation_horizontal_flip),
                            self.rgb_augmentation, self.drop_remainder)
-        return iter([ResidentBatch(self, index, flip, draws) for index, flip, draws in plan])
+        if self.random_crop is None:
+            return iter([ResidentBatch(self, index, flip, draws) for index, flip, draws in plan])
+        kw, fill = self.random_crop        # the windows come after the whole plan: the plan's draws are those of random_crop=None
+        return iter([ResidentBatch(self, index, flip, draws, crop_windows=random_crop_windows(self._rng, len(index), self.height, self.width, **kw),
+                                   crop_fill=fill) for index, flip, draws in plan])
 
     def to_compact(self, batch: ResidentBatch) -> CompactBatch:
-        """the named samples downloaded into an equal CompactBatch (same flips, same draws): for debugging and tests"""
+        """the named samples downloaded into an equal CompactBatch (same windows, same flips, same draws): for debugging and tests"""
         hw = self.height * self.width
         images = np.stack([self.images.view(int(i) * hw * 3, (self.height, self.width, 3)).download() for i in batch.index])
         masks = np.stack([self.masks.view(int(i) * hw, (self.height, self.width)).download() for i in batch.index])
         cnt = self.cnt.download()
         gts = [self.gt.view(int(i) * self.GMAX * 5, (self.GMAX, 5)).download()[:cnt[i]] for i in batch.index]
         flip = np.zeros(len(batch), np.uint8) if batch.flip is None else batch.flip.copy()
-        return CompactBatch(images, masks, gts, flip, self.encoder, rgb_draws=batch.rgb_draws)
+        return CompactBatch(images, masks, gts, flip, self.encoder, rgb_draws=batch.rgb_draws, crop_windows=batch.crop_windows,
+                            crop_fill=batch.crop_fill)
 
 
 def read_image(path_file_image: str) -> np.ndarray:

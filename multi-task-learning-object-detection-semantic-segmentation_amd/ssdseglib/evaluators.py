@@ -114,12 +114,14 @@ def _nms_layer(model_inference):
 
 
 def _check_plain(batch) -> None:
-    """evaluation is on the files as they are: no mirrored sample, no colour draws"""
+    """evaluation is on the files as they are: no mirrored sample, no colour draws, no crop windows"""
     kind = type(batch).__name__
     if kind not in ("CompactBatch", "ResidentBatch"):
         raise ValueError(f"evaluate_on_device takes CompactBatch / ResidentBatch objects or a ResidentDataset, got {kind}")
     if getattr(batch, "rgb_draws", None) is not None:
         raise ValueError("evaluate_on_device: the batch carries colour-augmentation draws")
+    if getattr(batch, "crop_windows", None) is not None:
+        raise ValueError("evaluate_on_device: the batch carries crop windows; a test set is not augmented")
     if batch.flip is not None and np.any(batch.flip):
         raise ValueError("evaluate_on_device: the batch has mirrored samples (flip flags set)")
 
@@ -152,7 +154,7 @@ def evaluate_on_device(model_inference, data, labels_codes: List[int], label_cod
     model_inference: from `get_model_for_inference` (suppress_background_boxes=False: with True the detections lose their batch
     axis, quirk Q7, and belong to no image; use_segmentation_suppression either way).  data: an iterable of
     `datacoder.CompactBatch`, a `ResidentDataset` (walked in slot order in its batch size, un-augmented, its generator untouched)
-    or an iterable of `ResidentBatch`; no flips, no colour draws.  nms_grid: (boxes_iou_threshold, labels_probability_threshold)
+    or an iterable of `ResidentBatch`; no flips, no colour draws, no crop windows (ValueError).  nms_grid: (boxes_iou_threshold, labels_probability_threshold)
     pairs, default the model's own.  Per batch the network and the decode (+ segmentation suppression) run once, the NMS once per
     pair; segmentation suppression is batch-wide (quirk Q6), so the detections are those of `predict` on the same batches.
 
