@@ -1,6 +1,7 @@
 // Internal helpers shared by the HIP translation units of libssdseg_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -126,7 +127,8 @@ void ssdseg_defer_hold(ssdseg_ctx* ctx, int delta);
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // Environment switches.  Read on every call, never cached: the parity tests flip them inside one process.
-// env_is: the variable is set and starts with `ch`;  env_int: its integer value, `fallback` when unset
+// env_is: the variable is set and starts with `ch`;  env_int: its integer value, `fallback` when unset;
+// env_pick: 1-based position of its value among `values`, 0 when unset or not one of them
 static inline bool env_is(const char* name, char ch) {
     const char* e = getenv(name);
     return e != nullptr && e[0] == ch;
@@ -134,6 +136,15 @@ static inline bool env_is(const char* name, char ch) {
 static inline long long env_int(const char* name, long long fallback) {
     const char* e = getenv(name);
     return e != nullptr ? atoll(e) : fallback;
+}
+static inline int env_pick(const char* name, std::initializer_list<const char*> values) {
+    const char* e = getenv(name);
+    int i = 0;
+    for (const char* v : values) {
+        ++i;
+        if (e != nullptr && !strcmp(e, v)) return i;
+    }
+    return 0;
 }
 
 // TF "SAME" geometry

@@ -312,30 +312,31 @@ __global__ void __launch_bounds__(512) dw_bwd_kernel(DwGeom gm, ViewDev in, cons
     }
 }
 
-struct DwLaunch {
-    dim3 grid, block;
-    size_t lds;
-};
+struct DwLaunch { dim3 grid, block; size_t lds; };
 
-bool dw_geometry(int n, int h, int w, int c, int stride, int dilation, DwGeom* g, DwLaunch* l) {
-    g->n = n; g->h = h; g->w = w; g->c = c; g->s = stride; g->d = dilation;
-    same_pad(h, 3, stride, dilation, &g->ho, &g->pt);
-    same_pad(w, 3, stride, dilation, &g->wo, &g->pl);
-    g->cv = c / 4;
-    g->wtiles = cdiv(g->wo, TW);
-    g->ntiles = (long long)n * g->ho * g->wtiles;
-    int bx = g->cv < 256 ? g->cv : 256;
+// sizes and pads of a call: what every family needs, and the kernel argument of all but the marching kernels
+DwGeom dw_geom(int n, int h, int w, int c, int stride, int dilation) {
+    DwGeom g;
+    g.n = n; g.h = h; g.w = w; g.c = c; g.s = stride; g.d = dilation;
+    same_pad(h, 3, stride, dilation, &g.ho, &g.pt);
+    same_pad(w, 3, stride, dilation, &g.wo, &g.pl);
+    g.cv = c / 4;
+    g.wtiles = cdiv(g.wo, TW);
+    g.ntiles = (long long)n * g.ho * g.wtiles;
+    return g;
+}
+
+// launch of the register-window and gather kernels
+DwLaunch reg_launch(const DwGeom& g) {
+    int bx = g.cv < 256 ? g.cv : 256;
     int by = 512 / bx;
     if (by > 64) by = 64;
     if (by < 1) by = 1;
-    long long want = (g->ntiles + by - 1) / by;
+    long long want = (g.ntiles + by - 1) / by;
     int gx = (int)(want < MAX_BLOCKS ? want : MAX_BLOCKS);
     if (gx < 1) gx = 1;
     gx = (gx + 7) & ~7;   // multiple of 8 for the XCD remap (surplus blocks find no tile and write zero partial rows)
-    l->block = dim3(bx, by, 1);
-    l->grid = dim3(gx, cdiv(g->cv, bx), 1);
-    l->lds = (size_t)bx * by * sizeof(float4);
-    return true;
+    return DwLaunch{dim3(gx, cdiv(g.cv, bx), 1), dim3(bx, by, 1), (size_t)bx * by * sizeof(float4)};
 }
 
 }  // namespace
@@ -343,26 +344,137 @@ bool dw_geometry(int n, int h, int w, int c, int stride, int dilation, DwGeom* g
 #include "dwconv_lds.h"
 #include "dwconv_march.h"
 
-#include <stdlib.h>
+#include <stdarg.h>
+#include <type_traits>
 
 namespace {
 
-// SSDSEG_DW_BWD=march|lds|reg forces one backward kernel family (A/B measurements); default: measured best per shape
-// (read on every call, not cached: the parity tests flip it between calls)
-int dw_bwd_choice() {
-    const char* e = getenv("SSDSEG_DW_BWD");
-    return !e ? 0 : (!strcmp(e, "march") ? 1 : (!strcmp(e, "lds") ? 2 : (!strcmp(e, "reg") ? 3 : 0)));
+// ------------------------------------------------------------------------------------------------ the plan of a call
+// Everything the host decides about one call, decided ONCE: the kernel family, that family's geometry and launch, the partial
+// rows it writes and the template flags of its kernel.  ssdseg_dwconv_parts, the zeroing of surplus statistics rows and the
+// launches all read it.  The switches are read on every call, not cached: the parity tests flip them between calls.
+enum DwFamily {
+    DW_MARCH,    // column-marching kernels (dwconv_march.h): the forward at both strides, the stride-1 backward (dilated: sub-grids)
+    DW_MARCH2,   // the stride-2 backward march
+    DW_LDS,      // LDS-tiled kernels (dwconv_lds.h), dense taps
+    DW_REG,      // register-window backward, dense taps
+    DW_GATHER    // direct gathers of the dilated convs (the DIL == 0 form of the register-window kernels)
+};
+struct DwPlan {
+    DwFamily family;
+    DwGeom g;           // every family: sizes and pads
+    MarchGeom mg;       // DW_MARCH backward
+    March2Geom mg2;     // DW_MARCH forward, DW_MARCH2
+    DwLaunch l;
+    int rows;           // partial rows the kernel writes (one per block along grid.x): BatchNorm statistics forward, dW backward
+    bool fuse, acc, wfull;   // backward marches: BNFUSE, ACC and WFULL of the kernel
+};
+
+// the marching kernels address with 32-bit byte offsets
+bool dw_march_fits(int n, int h, int w, int c) { return (long long)n * h * w * c < (1LL << 30); }
+
+// forward plan of one family (ssdseg_dwconv_parts asks for both candidates of a layer, a call for the one it runs)
+DwPlan dw_fwd_plan(DwFamily family, int n, int h, int w, int c, int stride, int dilation) {
+    DwPlan p{};
+    p.family = family;
+    p.g = dw_geom(n, h, w, c, stride, dilation);
+    if (family == DW_LDS) p.l = stride == 1 ? lds_launch<1>(p.g, true) : lds_launch<2>(p.g, true);
+    else if (family != DW_MARCH) p.l = reg_launch(p.g);
+    else {
+        p.mg2 = March2Geom{n, h, w, c, p.g.ho, p.g.wo};
+        p.l = march_geometry(&p.mg2, n, p.g.ho, p.g.wo, c, stride == 1 ? 4 : 2, 2, 4096, dilation);
+        p.mg2.depth2 = !env_is("SSDSEG_DW_FWD_DEPTH", '1');
+    }
+    p.rows = (int)p.l.grid.x;
+    return p;
 }
 
-// forward kernel family: column-marching for every dense-tap conv whose tensors fit 32-bit byte offsets
-// (SSDSEG_DW_FWD=lds keeps the LDS-tiled kernels for A/B measurements)
-bool dw_fwd_use_march(int n, int h, int w, int c, int dilation) {
-    const char* e = getenv("SSDSEG_DW_FWD");
-    const bool lds = e != nullptr && !strcmp(e, "lds");
-    const char* atr = getenv("SSDSEG_DW_ATROUS");   // "gather": direct-gather kernels for the dilated convs
-    const bool atrous_ok = !(atr != nullptr && !strcmp(atr, "gather"));
-    return !lds && (dilation == 1 || atrous_ok) && (long long)n * h * w * c < (1LL << 30);
+// forward family: column-marching for every conv whose tensors fit 32-bit byte offsets (SSDSEG_DW_FWD=lds keeps the LDS-tiled
+// kernels, SSDSEG_DW_ATROUS=gather the direct-gather kernel of the dilated convs: A/B measurements, parity tests)
+DwFamily dw_fwd_family(int n, int h, int w, int c, int dilation) {
+    const bool lds = env_pick("SSDSEG_DW_FWD", {"lds"}) != 0;
+    const bool atrous_ok = env_pick("SSDSEG_DW_ATROUS", {"gather"}) == 0;
+    if (!lds && (dilation == 1 || atrous_ok) && dw_march_fits(n, h, w, c)) return DW_MARCH;
+    return dilation == 1 ? DW_LDS : DW_GATHER;
 }
+
+// rows of the BatchNorm statistics table of a layer: the larger count of the two forward kernels that can take it, whatever the
+// switches say when the table is allocated (`have`: the plan the caller has made already)
+int dw_fwd_table_rows(int n, int h, int w, int c, int stride, int dilation, const DwPlan* have) {
+    int rows = 0;
+    for (DwFamily f : {DW_MARCH, dilation == 1 ? DW_LDS : DW_GATHER}) {
+        if (f == DW_MARCH && !dw_march_fits(n, h, w, c)) continue;
+        const int r = have != nullptr && have->family == f ? have->rows : dw_fwd_plan(f, n, h, w, c, stride, dilation).rows;
+        if (r > rows) rows = r;
+    }
+    return rows;
+}
+
+// backward plan.  SSDSEG_DW_BWD=march|lds|reg forces one kernel family (A/B measurements); default: measured best per shape
+DwPlan dw_bwd_plan(int n, int h, int w, int c, int stride, int dilation, bool has_dx, bool accumulate, bool has_bn) {
+    DwPlan p{};
+    p.g = dw_geom(n, h, w, c, stride, dilation);
+    const int choice = env_pick("SSDSEG_DW_BWD", {"march", "lds", "reg"});
+    const bool march = (choice == 0 || choice == 1) && dw_march_fits(n, h, w, c);
+    // atrous (stride 1, SAME: pad == dilation): dilation^2 interleaved dense convs through the same marching kernel
+    // (SSDSEG_DW_ATROUS=gather keeps the direct-gather kernel: nine two-tensor gathers per output pixel, 0.5 TB/s)
+    const bool atrous_march = dilation > 1 && env_pick("SSDSEG_DW_ATROUS", {"gather"}) == 0 && p.g.pt == dilation && p.g.pl == dilation &&
+                              p.g.ho == h && p.g.wo == w;
+    if (march && stride == 1 && (dilation == 1 || atrous_march)) {
+        p.family = DW_MARCH;
+        p.mg = MarchGeom{n, h, w, c};
+        p.l = march_geometry(&p.mg, n, h, w, c, MTW, 11, march_min_waves(), dilation);
+        p.fuse = has_bn && dilation == 1 && has_dx;   // (with accumulate: this conv is the LAST writer of dx)
+        p.acc = accumulate;
+        p.wfull = w % MTW == 0 && dilation == 1;
+    } else if (march && stride == 2 && dilation == 1) {
+        p.family = DW_MARCH2;
+        p.mg2 = March2Geom{n, h, w, c, p.g.ho, p.g.wo};
+        p.l = march_geometry(&p.mg2, n, p.g.ho, p.g.wo, c, 2, 11, 4096, 1);
+        p.fuse = has_bn && has_dx;
+        p.acc = accumulate && has_dx;
+    } else if (dilation == 1 && stride == 1 && (choice == 2 || (choice != 3 && c <= 160))) {
+        // measured on MI355X (profiles/): the fused LDS backward wins for stride 1 with few channel groups (big early layers,
+        // decoder); with many channel groups or stride 2 its 256-VGPR footprint loses to the register-window kernel
+        p.family = DW_LDS;
+        p.l = lds_launch<1>(p.g, false);
+    } else {
+        p.family = dilation == 1 ? DW_REG : DW_GATHER;
+        p.l = reg_launch(p.g);
+    }
+    p.rows = (int)p.l.grid.x;
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------ launches
+// run-time flags -> template arguments (the idiom of for_width in gemm_internal.h): f is a generic lambda over one
+// std::bool_constant per flag, and rules the combinations no plan names out with `if constexpr`, so that they are not compiled
+template <class F>
+int for_flags(F&& f) { return f(); }
+template <class F, class... Rest>
+int for_flags(F&& f, bool flag, Rest... rest) {
+    auto bind = [&](auto B) { return for_flags([&](auto... more) { return f(B, more...); }, rest...); };
+    return flag ? bind(std::true_type{}) : bind(std::false_type{});
+}
+#define FLAG(B) (decltype(B)::value)
+
+int dw_no_kernel(const char* which) {
+    ssdseg_set_error("%s: the plan names an instantiation that does not exist", which);
+    return SSDSEG_EINVAL(0);
+}
+
+// name of a template instance in the timing registry, spelled as SSDSEG_LAUNCH stringifies a literal one -- parentheses
+// included: "(dw_bwd_march_kernel<true, true, false, false>)" (bench.py and profiles/ key on these).  Built only while timing is on.
+const char* dw_kname(const ssdseg_ctx* ctx, const char* fmt, ...) {
+    if (!ctx->timing) return "";
+    char buf[96];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return ssdseg_intern(buf);
+}
+const char* tf(bool b) { return b ? "true" : "false"; }
 
 struct BnFuse {   // BatchNorm-backward reduction of the layer feeding this depthwise conv, fused into its backward
     const float* mean;
@@ -372,9 +484,9 @@ struct BnFuse {   // BatchNorm-backward reduction of the layer feeding this dept
 
 int dw_bwd_impl(ssdseg_ctx* ctx, const ssdseg_view* in, const float* w, const ssdseg_gview* dy, float* dx, float* dw, int n, int h,
                 int wdt, int c, int stride, int dilation, int accumulate, const BnFuse* bn, bool* bn_done) {
-    DwGeom g;
-    DwLaunch l;
-    dw_geometry(n, h, wdt, c, stride, dilation, &g, &l);
+    const DwPlan p = dw_bwd_plan(n, h, wdt, c, stride, dilation, dx != nullptr, accumulate != 0, bn != nullptr);
+    const DwGeom& g = p.g;
+    const DwLaunch& l = p.l;
     ViewDev v{in->x, in->scale, in->shift, in->act};
     GViewDev gv{dy->g, dy->y, dy->scale, dy->shift, dy->k1, dy->k0, dy->act};
     // algorithmic traffic, SURVEY.md 8(d): 4 * (2*X + Y + 18*C) -- read X, read dY, write dX, read W, write dW.  A BatchNorm-backward
@@ -383,124 +495,58 @@ int dw_bwd_impl(ssdseg_ctx* ctx, const ssdseg_view* in, const float* w, const ss
     const double cost_bytes = 4.0 * (2.0 * n * h * wdt * c + (double)n * g.ho * g.wo * c + 18.0 * c);
     ctx->timing_view_bytes = dy->scale != nullptr ? 4.0 * n * g.ho * g.wo * c : 0.0;
     const double cost_flops = 36.0 * n * g.ho * g.wo * c;
-    const int choice = dw_bwd_choice();
-    // atrous (stride 1, SAME: pad == dilation): dilation^2 interleaved dense convs through the same marching kernel
-    // (SSDSEG_DW_ATROUS=gather keeps the direct-gather kernel: nine two-tensor gathers per output pixel, 0.5 TB/s)
-    const char* atr = getenv("SSDSEG_DW_ATROUS");
-    const bool atrous_march = dilation > 1 && !(atr != nullptr && !strcmp(atr, "gather")) && g.pt == dilation && g.pl == dilation &&
-                              g.ho == h && g.wo == wdt;
-    const bool march_ok = (dilation == 1 || atrous_march) && stride == 1 && (long long)n * h * wdt * c < (1LL << 30);   // 32-bit byte offsets
     if (bn_done) *bn_done = false;
-    if (march_ok && (choice == 0 || choice == 1)) {
-        MarchGeom mg;
-        const MarchLaunch ml = march_geometry(n, h, wdt, c, &mg, dilation);
-        const int nparts = (int)ml.grid.x;
-        const bool fuse = bn != nullptr && dilation == 1 && dx != nullptr;   // (with accumulate: this conv is the LAST writer of dx)
-        void* ws;
-        int rc = ssdseg_partials(ctx, (size_t)nparts * 11 * c * sizeof(float), &ws);
-        if (rc) return rc;
-        float* part = (float*)ws;
-        float* bnpart = part + (size_t)nparts * 9 * c;
-        const bool wfull = wdt % MTW == 0 && dilation == 1;
-#define DW_BWD_MARCH(BN_, WF_, AC_, DIL_)                                                                                                        \
-    SSDSEG_LAUNCH(ctx, cost_bytes, cost_flops, (dw_bwd_march_kernel<BN_, WF_, AC_, DIL_>), ml.grid, ml.block, ml.lds, mg, v, w, gv, dx, part, accumulate, \
-                  fuse ? bn->mean : (const float*)nullptr, fuse ? bn->invstd : (const float*)nullptr, fuse ? bnpart : (float*)nullptr)
-        if (dilation > 1 && accumulate) DW_BWD_MARCH(false, false, true, true);
-        else if (dilation > 1) DW_BWD_MARCH(false, false, false, true);
-        else if (fuse && wfull && accumulate) DW_BWD_MARCH(true, true, true, false);
-        else if (fuse && accumulate) DW_BWD_MARCH(true, false, true, false);
-        else if (fuse && wfull) DW_BWD_MARCH(true, true, false, false);
-        else if (fuse) DW_BWD_MARCH(true, false, false, false);
-        else if (wfull && accumulate) DW_BWD_MARCH(false, true, true, false);
-        else if (wfull) DW_BWD_MARCH(false, true, false, false);
-        else if (accumulate) DW_BWD_MARCH(false, false, true, false);
-        else DW_BWD_MARCH(false, false, false, false);
-#undef DW_BWD_MARCH
-        SSDSEG_LAUNCH_CHECK();
-        rc = ssdseg_colsum(ctx, part, nparts, 9LL * c, dw);
-        if (rc || !fuse) return rc;
-        *bn_done = true;
-        return ssdseg_bn_bwd_finalize_launch(ctx, bnpart, nparts, c, (double)n * h * wdt, in->scale, bn->mean, bn->invstd, bn->dgamma,
-                                             bn->dbeta, bn->k1, bn->k0);
-    }
-    const bool march2_ok = dilation == 1 && stride == 2 && (long long)n * h * wdt * c < (1LL << 30);
-    if (march2_ok && (choice == 0 || choice == 1)) {
-        March2Geom mg;
-        const MarchLaunch ml = march2_geometry(n, h, wdt, c, g.ho, g.wo, &mg);
-        const int nparts = (int)ml.grid.x;
-        const bool fuse = bn != nullptr && dx != nullptr;
-        void* ws;
-        int rc = ssdseg_partials(ctx, (size_t)nparts * 11 * c * sizeof(float), &ws);
-        if (rc) return rc;
-        float* part = (float*)ws;
-        float* bnpart = part + (size_t)nparts * 9 * c;
-#define DW_BWD_MARCH2(BN_, PT_, PL_, AC_)                                                                                                     \
-    SSDSEG_LAUNCH(ctx, cost_bytes, cost_flops, (dw_bwd_march2_kernel<BN_, PT_, PL_, AC_>), ml.grid, ml.block, ml.lds, mg, v, w, gv, dx, part, \
-                  accumulate, fuse ? bn->mean : (const float*)nullptr, fuse ? bn->invstd : (const float*)nullptr,                          \
-                  fuse ? bnpart : (float*)nullptr)
-#define DW_BWD_MARCH2_P(BN_, AC_)                             \
-    do {                                                      \
-        if (g.pt == 0 && g.pl == 0) DW_BWD_MARCH2(BN_, 0, 0, AC_); \
-        else if (g.pt == 0) DW_BWD_MARCH2(BN_, 0, 1, AC_);    \
-        else if (g.pl == 0) DW_BWD_MARCH2(BN_, 1, 0, AC_);    \
-        else DW_BWD_MARCH2(BN_, 1, 1, AC_);                   \
-    } while (0)
-        if (fuse && accumulate) DW_BWD_MARCH2_P(true, true);
-        else if (fuse) DW_BWD_MARCH2_P(true, false);
-        else if (accumulate && dx != nullptr) DW_BWD_MARCH2_P(false, true);
-        else DW_BWD_MARCH2_P(false, false);
-#undef DW_BWD_MARCH2_P
-#undef DW_BWD_MARCH2
-        SSDSEG_LAUNCH_CHECK();
-        rc = ssdseg_colsum(ctx, part, nparts, 9LL * c, dw);
-        if (rc || !fuse) return rc;
-        *bn_done = true;
-        return ssdseg_bn_bwd_finalize_launch(ctx, bnpart, nparts, c, (double)n * h * wdt, in->scale, bn->mean, bn->invstd, bn->dgamma,
-                                             bn->dbeta, bn->k1, bn->k0);
-    }
-    const LdsLaunch ll = stride == 1 ? lds_launch<1>(g) : lds_launch<2>(g);
-    // measured on MI355X (profiles/): the fused LDS backward wins for stride 1 with few channel groups (big early layers,
-    // decoder); with many channel groups or stride 2 its 256-VGPR footprint loses to the register-window kernel
-    const bool use_lds = dilation == 1 && stride == 1 && (choice == 2 || (choice != 3 && c <= 160));
-    const int nparts = use_lds ? (int)ll.grid.x : (int)l.grid.x;
+    // partial table: [rows][9][c] of dW, and behind it the marching kernels' [rows][2][c] of the fused BatchNorm sums (requested
+    // by every march, fused or not)
+    const bool march = p.family == DW_MARCH || p.family == DW_MARCH2;
     void* ws;
-    size_t part_bytes = (size_t)nparts * 9 * c * sizeof(float);
-    int rc = ssdseg_partials(ctx, part_bytes, &ws);
+    int rc = ssdseg_partials(ctx, (size_t)p.rows * (march ? 11 : 9) * c * sizeof(float), &ws);
     if (rc) return rc;
     float* part = (float*)ws;
-#define DW_BWD_LDS(S_, PT_, PL_) \
-    SSDSEG_LAUNCH(ctx, cost_bytes, cost_flops, (dw_bwd_lds_kernel<S_, PT_, PL_>), ll.grid, dim3(256), ll.lds_bwd, g, v, w, gv, dx, part, accumulate)
-#define DW_BWD_REG(S_, D_, PT_, PL_) \
-    SSDSEG_LAUNCH(ctx, cost_bytes, cost_flops, (dw_bwd_kernel<S_, D_, PT_, PL_>), l.grid, l.block, l.lds, g, v, w, gv, dx, part, accumulate)
-    if (dilation != 1) DW_BWD_REG(1, 0, 0, 0);
-    else if (use_lds) DW_BWD_LDS(1, 1, 1);
-    else if (stride == 1) DW_BWD_REG(1, 1, 1, 1);
-    else if (g.pt == 0 && g.pl == 0) DW_BWD_REG(2, 1, 0, 0);
-    else if (g.pt == 0 && g.pl == 1) DW_BWD_REG(2, 1, 0, 1);
-    else if (g.pt == 1 && g.pl == 0) DW_BWD_REG(2, 1, 1, 0);
-    else DW_BWD_REG(2, 1, 1, 1);
-#undef DW_BWD_REG
-#undef DW_BWD_LDS
+    float* bnpart = p.fuse ? part + (size_t)p.rows * 9 * c : nullptr;
+    const float* mean = p.fuse ? bn->mean : nullptr;
+    const float* invstd = p.fuse ? bn->invstd : nullptr;
+    if (p.family == DW_MARCH) {
+        rc = for_flags([&](auto BN, auto WF, auto AC, auto DIL) {
+            constexpr bool exists = !(FLAG(DIL) && (FLAG(BN) || FLAG(WF)));     // (the dilated march: neither fused nor WFULL)
+            if constexpr (exists)
+                SSDSEG_LAUNCH_NAMED(ctx, dw_kname(ctx, "(dw_bwd_march_kernel<%s, %s, %s, %s>)", tf(FLAG(BN)), tf(FLAG(WF)), tf(FLAG(AC)), tf(FLAG(DIL))),
+                                    cost_bytes, cost_flops, (dw_bwd_march_kernel<FLAG(BN), FLAG(WF), FLAG(AC), FLAG(DIL)>), l.grid, l.block, l.lds,
+                                    p.mg, v, w, gv, dx, part, accumulate, mean, invstd, bnpart);
+            return exists ? 0 : dw_no_kernel("dw_bwd_march_kernel");
+        }, p.fuse, p.wfull, p.acc, dilation > 1);
+    } else if (p.family == DW_MARCH2) {
+        rc = for_flags([&](auto BN, auto PT, auto PL, auto AC) {
+            SSDSEG_LAUNCH_NAMED(ctx, dw_kname(ctx, "(dw_bwd_march2_kernel<%s, %d, %d, %s>)", tf(FLAG(BN)), (int)FLAG(PT), (int)FLAG(PL), tf(FLAG(AC))),
+                                cost_bytes, cost_flops, (dw_bwd_march2_kernel<FLAG(BN), FLAG(PT), FLAG(PL), FLAG(AC)>), l.grid, l.block, l.lds,
+                                p.mg2, v, w, gv, dx, part, accumulate, mean, invstd, bnpart);
+            return 0;
+        }, p.fuse, g.pt != 0, g.pl != 0, p.acc);
+    } else if (p.family == DW_LDS) {
+        SSDSEG_LAUNCH(ctx, cost_bytes, cost_flops, (dw_bwd_lds_kernel<1, 1, 1>), l.grid, l.block, l.lds, g, v, w, gv, dx, part, accumulate);
+    } else {
+        // <S, DIL, PT, PL>: gather <1, 0, 0, 0> (pads at run time) | stride 1 <1, 1, 1, 1> | stride 2 <2, 1, pt, pl>
+        const bool dense = p.family == DW_REG;
+        rc = for_flags([&](auto S2, auto DENSE, auto PT, auto PL) {
+            constexpr bool exists = FLAG(DENSE) ? (FLAG(S2) || (FLAG(PT) && FLAG(PL))) : (!FLAG(S2) && !FLAG(PT) && !FLAG(PL));
+            constexpr int S = FLAG(S2) ? 2 : 1;
+            if constexpr (exists)
+                SSDSEG_LAUNCH_NAMED(ctx, dw_kname(ctx, "(dw_bwd_kernel<%d, %d, %d, %d>)", S, (int)FLAG(DENSE), (int)FLAG(PT), (int)FLAG(PL)), cost_bytes,
+                                    cost_flops, (dw_bwd_kernel<S, FLAG(DENSE), FLAG(PT), FLAG(PL)>), l.grid, l.block, l.lds, g, v, w, gv, dx, part,
+                                    accumulate);
+            return exists ? 0 : dw_no_kernel("dw_bwd_kernel");
+        }, stride == 2, dense, dense && (stride == 1 || g.pt != 0), dense && (stride == 1 || g.pl != 0));
+    }
+    if (rc) return rc;
     SSDSEG_LAUNCH_CHECK();
-    return ssdseg_colsum(ctx, part, nparts, 9LL * c, dw);
+    rc = ssdseg_colsum(ctx, part, p.rows, 9LL * c, dw);
+    if (rc || !p.fuse) return rc;
+    *bn_done = true;
+    return ssdseg_bn_bwd_finalize_launch(ctx, bnpart, p.rows, c, (double)n * h * wdt, in->scale, bn->mean, bn->invstd, bn->dgamma,
+                                         bn->dbeta, bn->k1, bn->k0);
 }
 
 }  // namespace
-
-// one block per partial row of the BatchNorm statistics table: rows written by each forward kernel (0 where it cannot take the layer)
-enum { DW_FWD_MARCH_K, DW_FWD_LDS_K, DW_FWD_GATHER_K };
-static int dw_fwd_rows(int n, int h, int w, int c, int stride, int dilation, int kind) {
-    DwGeom g;
-    DwLaunch l;
-    dw_geometry(n, h, w, c, stride, dilation, &g, &l);
-    if (kind == DW_FWD_MARCH_K) {                                        // column-marching kernels
-        if ((long long)n * h * w * c >= (1LL << 30)) return 0;
-        March2Geom mg;
-        return (int)march_fwd_geometry(n, h, w, c, g.ho, g.wo, stride, &mg, dilation).grid.x;
-    }
-    if (kind == DW_FWD_LDS_K) return dilation == 1 ? (int)(stride == 1 ? lds_launch<1>(g) : lds_launch<2>(g)).grid.x : 0;   // LDS-tiled
-    return dilation > 1 ? (int)l.grid.x : 0;                                                                              // gather
-}
 
 extern "C" {
 
@@ -510,11 +556,8 @@ int ssdseg_dwconv_parts(int n, int h, int w, int c, int stride, int dilation, in
     SSDSEG_ARG(stride == 1 || stride == 2, 5);
     SSDSEG_ARG(dilation >= 1 && (dilation == 1 || stride == 1), 6);
     SSDSEG_ARG(nparts_host != nullptr, 7);
-    // sized for whichever forward kernel may run, whatever the dispatch switches say when the table is allocated
     // (ssdseg_dwconv_fwd zeroes the rows the launched kernel does not write)
-    int rows = dw_fwd_rows(n, h, w, c, stride, dilation, DW_FWD_MARCH_K);
-    const int other = dw_fwd_rows(n, h, w, c, stride, dilation, dilation == 1 ? DW_FWD_LDS_K : DW_FWD_GATHER_K);
-    *nparts_host = rows > other ? rows : other;
+    *nparts_host = dw_fwd_table_rows(n, h, w, c, stride, dilation, nullptr);
     return 0;
 }
 
@@ -531,44 +574,41 @@ int ssdseg_dwconv_fwd(ssdseg_ctx* ctx, const ssdseg_view* in, const float* w, fl
     SSDSEG_ARG(stride == 1 || stride == 2, 9);
     SSDSEG_ARG(dilation >= 1 && (dilation == 1 || stride == 1), 10);
     SSDSEG_ARG((in->scale == nullptr) == (in->shift == nullptr), 2);
-    DwGeom g;
-    DwLaunch l;
-    dw_geometry(n, h, wdt, c, stride, dilation, &g, &l);
+    const DwPlan p = dw_fwd_plan(dw_fwd_family(n, h, wdt, c, dilation), n, h, wdt, c, stride, dilation);
+    const DwGeom& g = p.g;
+    const DwLaunch& l = p.l;
     ViewDev v{in->x, in->scale, in->shift, in->act};
     // algorithmic traffic: read X, write Y, read W
     const double cost_bytes = 4.0 * ((double)n * h * wdt * c + (double)n * g.ho * g.wo * c + 9.0 * c);
     const double cost_flops = 18.0 * n * g.ho * g.wo * c;
-    const bool march = dw_fwd_use_march(n, h, wdt, c, dilation);
     if (stats != nullptr) {      // the table is sized for the largest candidate (ssdseg_dwconv_parts): the rows this launch does not write are zero
-        int nparts = 0;
-        int rc = ssdseg_dwconv_parts(n, h, wdt, c, stride, dilation, &nparts);
-        if (rc) return rc;
-        const int mine = dw_fwd_rows(n, h, wdt, c, stride, dilation, march ? DW_FWD_MARCH_K : (dilation == 1 ? DW_FWD_LDS_K : DW_FWD_GATHER_K));
-        if (nparts > mine) SSDSEG_HIP(hipMemsetAsync(stats + (size_t)mine * 2 * c, 0, (size_t)(nparts - mine) * 2 * c * sizeof(float), ctx->stream));
+        const int nparts = dw_fwd_table_rows(n, h, wdt, c, stride, dilation, &p);
+        if (nparts > p.rows) SSDSEG_HIP(hipMemsetAsync(stats + (size_t)p.rows * 2 * c, 0, (size_t)(nparts - p.rows) * 2 * c * sizeof(float), ctx->stream));
     }
-    if (march) {
-        March2Geom mg;
-        const MarchLaunch ml = march_fwd_geometry(n, h, wdt, c, g.ho, g.wo, stride, &mg, dilation);
-        { const char* e = getenv("SSDSEG_DW_FWD_DEPTH"); mg.depth2 = !(e != nullptr && e[0] == '1'); }
-#define DW_FWD_MARCH(S_, PT_, PL_, DIL_) \
-    SSDSEG_LAUNCH(ctx, cost_bytes, cost_flops, (dw_fwd_march_kernel<S_, PT_, PL_, DIL_>), ml.grid, ml.block, ml.lds, mg, v, w, y, stats)
-        if (dilation > 1) DW_FWD_MARCH(1, 1, 1, true);
-        else if (stride == 1 && mg.depth2) SSDSEG_LAUNCH(ctx, cost_bytes, cost_flops, (dw_fwd_march_kernel<1, 1, 1, false, true>), ml.grid, ml.block, ml.lds, mg, v, w, y, stats);
-        else if (stride == 1) DW_FWD_MARCH(1, 1, 1, false);
-        else if (g.pt == 0 && g.pl == 0) DW_FWD_MARCH(2, 0, 0, false);
-        else if (g.pt == 0) DW_FWD_MARCH(2, 0, 1, false);
-        else if (g.pl == 0) DW_FWD_MARCH(2, 1, 0, false);
-        else DW_FWD_MARCH(2, 1, 1, false);
-#undef DW_FWD_MARCH
-    } else if (dilation == 1 && stride == 1) {
-        const LdsLaunch ll = lds_launch<1>(g);
-        SSDSEG_LAUNCH(ctx, cost_bytes, cost_flops, (dw_fwd_lds_kernel<1>), ll.grid, dim3(256), ll.lds_fwd, g, v, w, y, stats);
-    } else if (dilation == 1) {
-        const LdsLaunch ll = lds_launch<2>(g);
-        SSDSEG_LAUNCH(ctx, cost_bytes, cost_flops, (dw_fwd_lds_kernel<2>), ll.grid, dim3(256), ll.lds_fwd, g, v, w, y, stats);
+    int rc = 0;
+    if (p.family == DW_MARCH) {
+        // <S, PT, PL, DIL, D2>: stride 1 <1, 1, 1, dilated, two rows ahead (dense taps only)> | stride 2 <2, pt, pl, false, false>
+        const bool s2 = stride == 2, dil = dilation > 1;
+        rc = for_flags([&](auto S2, auto PT, auto PL, auto DIL, auto D2) {
+            constexpr bool exists = FLAG(S2) ? (!FLAG(DIL) && !FLAG(D2)) : (FLAG(PT) && FLAG(PL) && !(FLAG(DIL) && FLAG(D2)));
+            constexpr int S = FLAG(S2) ? 2 : 1;
+            if constexpr (exists)      // (D2 = false is the template's default and is not spelled in the name)
+                SSDSEG_LAUNCH_NAMED(ctx, dw_kname(ctx, "(dw_fwd_march_kernel<%d, %d, %d, %s%s>)", S, (int)FLAG(PT), (int)FLAG(PL), tf(FLAG(DIL)), FLAG(D2) ? ", true" : ""),
+                                    cost_bytes, cost_flops, (dw_fwd_march_kernel<S, FLAG(PT), FLAG(PL), FLAG(DIL), FLAG(D2)>), l.grid, l.block, l.lds, p.mg2,
+                                    v, w, y, stats);
+            return exists ? 0 : dw_no_kernel("dw_fwd_march_kernel");
+        }, s2, !s2 || g.pt != 0, !s2 || g.pl != 0, dil, !s2 && !dil && p.mg2.depth2 != 0);
+    } else if (p.family == DW_LDS) {
+        rc = for_flags([&](auto S2) {
+            constexpr int S = FLAG(S2) ? 2 : 1;
+            SSDSEG_LAUNCH_NAMED(ctx, dw_kname(ctx, "(dw_fwd_lds_kernel<%d>)", S), cost_bytes, cost_flops, (dw_fwd_lds_kernel<S>), l.grid, l.block, l.lds, g, v, w,
+                                y, stats);
+            return 0;
+        }, stride == 2);
     } else {
         SSDSEG_LAUNCH(ctx, cost_bytes, cost_flops, (dw_fwd_kernel<1, 0>), l.grid, l.block, l.lds, g, v, w, y, stats);
     }
+    if (rc) return rc;
     SSDSEG_LAUNCH_CHECK();
     return 0;
 }

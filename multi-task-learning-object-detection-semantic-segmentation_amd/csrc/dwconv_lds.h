@@ -281,15 +281,11 @@ __global__ void __launch_bounds__(256) dw_bwd_lds_kernel(DwGeom gm, ViewDev in, 
     }
 }
 
-struct LdsLaunch {
-    dim3 grid;
-    size_t lds_fwd, lds_bwd;
-};
-
+// launch of the LDS-tiled kernels (256 threads): the forward's input tile (at least the statistics reduction scratch), or the
+// backward's input tile + dy tile + strip reduction
 template <int S>
-LdsLaunch lds_launch(const DwGeom& g) {
+DwLaunch lds_launch(const DwGeom& g, bool fwd) {
     using T = LTile<S>;
-    LdsLaunch l;
     const long long tiles = (long long)g.n * ((g.ho + T::TH - 1) / T::TH) * ((g.wo + LTW - 1) / LTW);
     const int cgroups = (g.c + LCV * 4 - 1) / (LCV * 4);
     long long gx = tiles < 1024 ? tiles : 1024;            // also the number of BN-stat / dW partial rows
@@ -298,12 +294,9 @@ LdsLaunch lds_launch(const DwGeom& g) {
     if (gx > tiles) gx = tiles;
     if (gx < 1) gx = 1;
     gx = (gx + 7) & ~7LL;   // multiple of 8 for the XCD remap (surplus blocks find no tile and write zero partial rows)
-    l.grid = dim3((unsigned)gx, cgroups, 1);
-    l.lds_fwd = (size_t)T::IH * T::IW * LPS * sizeof(float4);
-    l.lds_bwd = l.lds_fwd + (size_t)(T::DH * T::DW * LPS + 15 * LCV) * sizeof(float4);
-    const size_t red = 256 * sizeof(float4);
-    if (l.lds_fwd < red) l.lds_fwd = red;
-    return l;
+    const size_t tile = (size_t)T::IH * T::IW * LPS * sizeof(float4), red = 256 * sizeof(float4);
+    return DwLaunch{dim3((unsigned)gx, cgroups, 1), dim3(256),
+                    fwd ? (tile < red ? red : tile) : tile + (size_t)(T::DH * T::DW * LPS + 15 * LCV) * sizeof(float4)};
 }
 
 }  // namespace

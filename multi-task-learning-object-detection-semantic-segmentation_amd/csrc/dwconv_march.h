@@ -217,20 +217,13 @@ __global__ void __launch_bounds__(MARCH_MAX_THREADS) __attribute__((amdgpu_waves
     }
 }
 
-struct MarchLaunch {
-    dim3 grid, block;
-    size_t lds;
-};
-
 // Block shape of the marching kernels: `cb` channels x `spb` ADJACENT column strips.  Strips of one block march in step, so
 // the horizontal halo between them is served by L1; between blocks it is not (neighbouring blocks drift apart by more rows
 // than L2 holds: PMC FETCH_SIZE showed the full 6/4 halo for one-strip blocks, 1.05x for the eight-strip blocks of c = 32).
 // So: channel chunks of 64 (one wave = one strip's 256-byte pixel segment, line-aligned because c % 64 == 0), as many
 // strips as fit in MARCH_MAX_THREADS, the count chosen to waste the fewest strip slots in the last group of a row.
-inline long long march_min_waves() {   // row chunking stops once the launch has this many waves (A/B: SSDSEG_MARCH_WAVES)
-    static const long long v = getenv("SSDSEG_MARCH_WAVES") ? atoll(getenv("SSDSEG_MARCH_WAVES")) : 4096;
-    return v;
-}
+// min_waves of the stride-1 backward (A/B: SSDSEG_MARCH_WAVES, read once; the forward and the stride-2 backward keep 4096)
+inline long long march_min_waves() { static const long long v = env_int("SSDSEG_MARCH_WAVES", 4096); return v; }
 inline void march_split(int c, int wstrips, int* cb_out, int* spb_out, int* cchunks_out) {
     static const int env_cb = getenv("SSDSEG_MARCH_CB") ? atoi(getenv("SSDSEG_MARCH_CB")) : 0;        // A/B switches
     static const int env_mt = getenv("SSDSEG_MARCH_MAXT") ? atoi(getenv("SSDSEG_MARCH_MAXT")) : 0;
@@ -254,29 +247,29 @@ inline void march_split(int c, int wstrips, int* cb_out, int* spb_out, int* cchu
     *cb_out = cb; *spb_out = best; *cchunks_out = cchunks;
 }
 
-// geometry for an n x h x w x c tensor: channel chunks of <= 256, as many strips per block as fit in 256 threads, row chunks
-// sized so that the launch has >= ~4096 waves (16 per CU) where the layer is big enough
-inline MarchLaunch march_geometry(int n, int h, int w, int c, MarchGeom* g, int dil = 1) {
-    g->n = n; g->h = h; g->w = w; g->c = c; g->dil = dil;
-    const int subs = dil * dil;
-    h = cdiv(h, dil); w = cdiv(w, dil);   // the largest sub-grid
-    n *= subs;
-    g->wstrips = cdiv(w, MTW);
+// THE geometry of the marching kernels, G = MarchGeom | March2Geom (the caller has filled in the tensor sizes): `rows` x `cols`
+// pixels per image to march over in strips of `strip` columns (input pixels for the stride-1 backward, output pixels for the
+// forward and the stride-2 backward), channel chunks of <= 256, as many strips per block as fit in 256 threads, `lds_floats`
+// floats of reduction scratch per thread, row chunks halved until the launch has `min_waves` waves (4096 = 16 per CU) where the
+// layer is big enough.  dil > 1 folds the conv into its dil^2 sub-grids (MarchGeom::dil): the largest one sets the geometry.
+template <class G>
+inline DwLaunch march_geometry(G* g, int n, int rows, int cols, int c, int strip, int lds_floats, long long min_waves, int dil) {
+    g->dil = dil;
+    n *= dil * dil;
+    rows = cdiv(rows, dil); cols = cdiv(cols, dil);
+    g->wstrips = cdiv(cols, strip);
     int cchunks;
     march_split(c, g->wstrips, &g->cb, &g->spb, &cchunks);
     g->sgroups = cdiv(g->wstrips, g->spb);
     const int threads = ((g->cb * g->spb + 63) / 64) * 64;
     const long long waves_per_chunkrow = (long long)n * g->sgroups * cchunks * (threads / 64);
-    int rows = h;
-    while (rows > 8 && waves_per_chunkrow * cdiv(h, rows) < march_min_waves()) rows = (rows + 1) / 2;
-    g->rows = rows;
-    g->chunks = cdiv(h, rows);
+    int chunk = rows;
+    while (chunk > 8 && waves_per_chunkrow * cdiv(rows, chunk) < min_waves) chunk = (chunk + 1) / 2;
+    g->rows = chunk;
+    g->chunks = cdiv(rows, chunk);
     g->sblocks = n * g->chunks * g->sgroups;
-    MarchLaunch l;
-    l.grid = dim3((unsigned)((g->sblocks + 7) & ~7), cchunks, 1);   // multiple of 8 for the XCD remap
-    l.block = dim3(threads, 1, 1);
-    l.lds = (size_t)11 * threads * sizeof(float);
-    return l;
+    return DwLaunch{dim3((unsigned)((g->sblocks + 7) & ~7), cchunks, 1),   // multiple of 8 for the XCD remap
+                    dim3(threads, 1, 1), (size_t)lds_floats * threads * sizeof(float)};
 }
 
 // ------------------------------------------------------------------------------------------------ stride 2
@@ -677,49 +670,6 @@ __global__ void __launch_bounds__(MARCH_MAX_THREADS) __attribute__((amdgpu_waves
             stats[((long long)bpos.x * 2 + 1) * gm.c + ch] = q;
         }
     }
-}
-
-// forward geometry: strips of OC output columns
-inline MarchLaunch march_fwd_geometry(int n, int h, int w, int c, int ho, int wo, int stride, March2Geom* g, int dil = 1) {
-    g->n = n; g->h = h; g->w = w; g->c = c; g->ho = ho; g->wo = wo; g->dil = dil;
-    n *= dil * dil;                            // (dil > 1: stride 1, ho == h, wo == w; the largest sub-grid sets the geometry)
-    ho = cdiv(ho, dil); wo = cdiv(wo, dil);
-    g->wstrips = cdiv(wo, stride == 1 ? 4 : 2);
-    int cchunks;
-    march_split(c, g->wstrips, &g->cb, &g->spb, &cchunks);
-    g->sgroups = cdiv(g->wstrips, g->spb);
-    const int threads = ((g->cb * g->spb + 63) / 64) * 64;
-    const long long waves_per_chunkrow = (long long)n * g->sgroups * cchunks * (threads / 64);
-    int rows = ho;
-    while (rows > 8 && waves_per_chunkrow * cdiv(ho, rows) < 4096) rows = (rows + 1) / 2;
-    g->rows = rows;
-    g->chunks = cdiv(ho, rows);
-    g->sblocks = n * g->chunks * g->sgroups;
-    MarchLaunch l;
-    l.grid = dim3((unsigned)((g->sblocks + 7) & ~7), cchunks, 1);
-    l.block = dim3(threads, 1, 1);
-    l.lds = (size_t)2 * threads * sizeof(float);
-    return l;
-}
-
-inline MarchLaunch march2_geometry(int n, int h, int w, int c, int ho, int wo, March2Geom* g) {
-    g->n = n; g->h = h; g->w = w; g->c = c; g->ho = ho; g->wo = wo; g->dil = 1;
-    g->wstrips = cdiv(wo, 2);
-    int cchunks;
-    march_split(c, g->wstrips, &g->cb, &g->spb, &cchunks);
-    g->sgroups = cdiv(g->wstrips, g->spb);
-    const int threads = ((g->cb * g->spb + 63) / 64) * 64;
-    const long long waves_per_chunkrow = (long long)n * g->sgroups * cchunks * (threads / 64);
-    int rows = ho;
-    while (rows > 8 && waves_per_chunkrow * cdiv(ho, rows) < 4096) rows = (rows + 1) / 2;
-    g->rows = rows;
-    g->chunks = cdiv(ho, rows);
-    g->sblocks = n * g->chunks * g->sgroups;
-    MarchLaunch l;
-    l.grid = dim3((unsigned)((g->sblocks + 7) & ~7), cchunks, 1);
-    l.block = dim3(threads, 1, 1);
-    l.lds = (size_t)11 * threads * sizeof(float);
-    return l;
 }
 
 }  // namespace
