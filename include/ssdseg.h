@@ -362,6 +362,24 @@ int ssdseg_softmax_rows(ssdseg_ctx* ctx, const ssdseg_view* in, float* out, int 
 int ssdseg_det_loss(ssdseg_ctx* ctx, const float* y_labels, const float* p_labels, const float* y_boxes,
                     const float* p_boxes, int b, int a, int c, float loss_scale, float* conf_loss, float* loc_loss,
                     float* d_logits, float* d_boxes, uint8_t* keep_mask);
+/* ssdseg_det_loss with a weight of its own per output: d_logits is scaled by conf_scale, d_boxes by loc_scale (compile's
+ * loss_weights may differ between 'output-labels' and 'output-boxes').  ssdseg_det_loss is this call with both scales equal. */
+int ssdseg_det_loss_scaled(ssdseg_ctx* ctx, const float* y_labels, const float* p_labels, const float* y_boxes,
+                           const float* p_boxes, int b, int a, int c, float conf_scale, float loc_scale, float* conf_loss,
+                           float* loc_loss, float* d_logits, float* d_boxes, uint8_t* keep_mask);
+/* Focal confidence loss (not in the reference) + localization_loss, forward and gradient in one call.  With ph = clip(p, eps,
+ * 1 - eps), eps = 1e-7 (the clip of confidence_loss):
+ *   per anchor  FL = -sum_c alpha_c y_c (1 - ph_c)^gamma log ph_c
+ *   per image   conf_loss[i] = sum over ALL anchors of FL / max(#non-background anchors of image i, 1)
+ * No hard-negative mining: every anchor contributes, background included, and no image depends on another one.
+ *   dFL/dp_c = g_c = -alpha_c y_c inside(p_c) [ (1 - ph_c)^gamma / ph_c - gamma (1 - ph_c)^(gamma - 1) log ph_c ]
+ *   d_logits_j = conf_scale / max(npos_i, 1) * p_j (g_j - sum_k p_k g_k)
+ * inside(p) = 1 for eps <= p <= 1 - eps, else 0 (the gradient of the clip).  gamma = 0, alpha = 1 is the softmax cross-entropy
+ * over every anchor; the gamma term is then exactly 0.  alpha4_host: four finite weights >= 0; gamma finite, >= 0.
+ * loc_loss and d_boxes (scaled by loc_scale) are bit-identical to ssdseg_det_loss's.  Any of the four outputs may be NULL. */
+int ssdseg_det_loss_focal(ssdseg_ctx* ctx, const float* y_labels, const float* p_labels, const float* y_boxes,
+                          const float* p_boxes, int b, int a, int c, const float* alpha4_host, float gamma, float conf_scale,
+                          float loc_scale, float* conf_loss, float* loc_loss, float* d_logits, float* d_boxes);
 /* exact top-k selection used by the mining step (tf.math.top_k semantics: larger value first, lower index
  * first among equals, losses.py:131): mask[i] = 1 for the k selected entries of values[n]. */
 int ssdseg_topk_mask(ssdseg_ctx* ctx, const float* values, int n, int k, uint8_t* mask);

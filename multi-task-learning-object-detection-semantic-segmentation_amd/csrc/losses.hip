@@ -3,6 +3,7 @@
 //                                                   background anchors of the WHOLE batch with the highest loss)
 //   localization_loss reference losses.py:5-49     (smooth-L1 over non-background anchors / #non-background)
 //   dice, dice_square reference losses.py:175-264  (API surface)
+//   focal confidence loss (not in the reference)   (every anchor contributes, no selection: see focal_prep_kernel)
 // Integer/selection work is exact: the k-th largest value is found by an MSB-first radix select on order-preserving
 // 32-bit keys and ties are broken by the lower index, which is tf.math.top_k's rule.
 // All float reductions are two-level with a fixed order (no float atomics).
@@ -41,6 +42,11 @@ struct AnchorTerms {
     float ce, is_bg, not_bg, sl1, loc_nb;
 };
 
+// 1 for an anchor that carries a box target (localization_loss's own non-background test, losses.py:23-24)
+__device__ __forceinline__ float has_box(float4 yb) { return (fabsf(yb.x) + fabsf(yb.y) + fabsf(yb.z) + fabsf(yb.w)) > 0.f ? 1.f : 0.f; }
+
+// WITH_CE = false leaves t.ce at 0 (the focal loss has its own confidence term and ranks nothing)
+template <bool WITH_CE = true>
 __device__ __forceinline__ AnchorTerms anchor_terms(float4 yl, float4 p, float4 yb, float4 pb) {
     AnchorTerms t;
     t.is_bg = yl.x;
@@ -50,8 +56,9 @@ __device__ __forceinline__ AnchorTerms anchor_terms(float4 yl, float4 p, float4 
     // approximation whose last bit differs between math libraries (ocml here, NumPy / Eigen elsewhere), which would make the
     // selected SET library-dependent.  The key is therefore defined as the correctly rounded float32 logarithm, obtained as
     // float(log(double(p))) -- reproducible by any host with an IEEE double log (the oracle does the same).
-    t.ce = -(yl.x * logcr(clipf(p.x)) + yl.y * logcr(clipf(p.y)) + yl.z * logcr(clipf(p.z)) + yl.w * logcr(clipf(p.w)));
-    t.loc_nb = (fabsf(yb.x) + fabsf(yb.y) + fabsf(yb.z) + fabsf(yb.w)) > 0.f ? 1.f : 0.f;
+    t.ce = 0.f;
+    if (WITH_CE) t.ce = -(yl.x * logcr(clipf(p.x)) + yl.y * logcr(clipf(p.y)) + yl.z * logcr(clipf(p.z)) + yl.w * logcr(clipf(p.w)));
+    t.loc_nb = has_box(yb);
     const float e[4] = {yb.x - pb.x, yb.y - pb.y, yb.z - pb.z, yb.w - pb.w};
     float s = 0.f;
 #pragma unroll
@@ -61,6 +68,18 @@ __device__ __forceinline__ AnchorTerms anchor_terms(float4 yl, float4 p, float4 
     }
     t.sl1 = s;
     return t;
+}
+
+// d smooth-L1 / d p_boxes of one anchor, times s (shared by the mined and the focal gradient pass: the same bits)
+__device__ __forceinline__ float4 sl1_grad(float s, float4 ybx, float4 pbx) {
+    const float e[4] = {ybx.x - pbx.x, ybx.y - pbx.y, ybx.z - pbx.z, ybx.w - pbx.w};
+    float d[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float ab = fabsf(e[k]);
+        d[k] = s * (ab < 1.f ? -e[k] : (e[k] > 0.f ? -1.f : (e[k] < 0.f ? 1.f : 0.f)));
+    }
+    return make_float4(d[0], d[1], d[2], d[3]);
 }
 
 // pass 1: per-anchor cross-entropy, background loss vector, per-block partial sums, batch-global counts
@@ -247,7 +266,8 @@ int topk_mask_launch(ssdseg_ctx* ctx, const float* v, int n, int k_host, const i
 // pass 2: gradients and the kept-background loss
 __global__ void __launch_bounds__(256) det_final_kernel(const float* __restrict__ yl, const float* __restrict__ pl, const float* __restrict__ yb,
                                                         const float* __restrict__ pb, int a, const unsigned char* __restrict__ mask,
-                                                        const float* __restrict__ img_stats, float loss_scale, float* __restrict__ d_logits,
+                                                        const float* __restrict__ img_stats, float conf_scale, float loc_scale,
+                                                        float* __restrict__ d_logits,
                                                         float* __restrict__ d_boxes, float* __restrict__ partial2) {
     __shared__ float red[256];
     const int img = blockIdx.y;
@@ -263,22 +283,12 @@ __global__ void __launch_bounds__(256) det_final_kernel(const float* __restrict_
         const float keep = (float)mask[(long long)img * a + i];
         acc[0] += t.ce * t.is_bg * keep;
         if (d_logits) {
-            const float sel = (t.not_bg + t.is_bg * keep) * inv_conf * loss_scale;
+            const float sel = (t.not_bg + t.is_bg * keep) * inv_conf * conf_scale;
             const float4 yi = make_float4(y.x * insidef(p.x), y.y * insidef(p.y), y.z * insidef(p.z), y.w * insidef(p.w));
             const float tot = yi.x + yi.y + yi.z + yi.w;
             st4(d_logits + o, make_float4(sel * (p.x * tot - yi.x), sel * (p.y * tot - yi.y), sel * (p.z * tot - yi.z), sel * (p.w * tot - yi.w)));
         }
-        if (d_boxes) {
-            const float s = t.loc_nb * inv_loc * loss_scale;
-            const float e[4] = {ybx.x - pbx.x, ybx.y - pbx.y, ybx.z - pbx.z, ybx.w - pbx.w};
-            float d[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float ab = fabsf(e[k]);
-                d[k] = s * (ab < 1.f ? -e[k] : (e[k] > 0.f ? -1.f : (e[k] < 0.f ? 1.f : 0.f)));
-            }
-            st4(d_boxes + o, make_float4(d[0], d[1], d[2], d[3]));
-        }
+        if (d_boxes) st4(d_boxes + o, sl1_grad(t.loc_nb * inv_loc * loc_scale, ybx, pbx));
     }
     block_sum<1>(acc, red);
     if (threadIdx.x == 0) partial2[(long long)img * gridDim.x + blockIdx.x] = acc[0];
@@ -293,6 +303,96 @@ __global__ void det_finish_kernel(const float* __restrict__ img_stats, const flo
     const float* s = img_stats + img * 4;
     if (conf_loss) conf_loss[img] = (s[0] + bg) / fmaxf(s[1], 1.f);
     if (loc_loss) loc_loss[img] = s[2] / fmaxf(s[3], 1.f);
+}
+
+// ---- focal confidence loss: FL = -sum_c alpha_c y_c (1 - ph_c)^gamma log ph_c with ph = clip(p), summed over EVERY anchor of an
+// image and divided by max(#non-background, 1).  No selection, so nothing couples the images of a batch: three launches
+// (per-block partials, per-image fold, gradient) against the mined loss's ten and two memsets, and no per-anchor scratch.  The
+// localization half is the mined loss's, expression for expression and in the same reduction order.
+struct FocalParams {
+    float alpha[4];
+    float gamma;
+};
+
+// one class of one anchor; y == 0 contributes nothing and skips the transcendental work (the targets are one-hot)
+__device__ __forceinline__ float focal_term(float y, float p, float alpha, float gamma) {
+    if (y == 0.f) return 0.f;
+    const float ph = clipf(p);
+    return -alpha * y * powf(1.f - ph, gamma) * logf(ph);   // 1 - ph >= 2^-23: powf never sees 0; powf(., 0) == 1
+}
+
+// d FL / d p_c = -alpha y inside(p) [ (1-ph)^gamma / ph - gamma (1-ph)^(gamma-1) log ph ]; the second term is exactly 0 at gamma = 0
+__device__ __forceinline__ float focal_grad(float y, float p, float alpha, float gamma) {
+    if (y == 0.f) return 0.f;
+    const float ph = clipf(p), q = 1.f - ph;
+    const float slope = gamma > 0.f ? gamma * powf(q, gamma - 1.f) * logf(ph) : 0.f;
+    return -alpha * y * insidef(p) * (powf(q, gamma) / ph - slope);
+}
+
+// pass 1: per-block partial sums (focal, #non-background, smooth-L1, #box anchors); the counts are sums of 0 / 1 floats, exact
+__global__ void __launch_bounds__(256) focal_prep_kernel(const float* __restrict__ yl, const float* __restrict__ pl, const float* __restrict__ yb,
+                                                         const float* __restrict__ pb, int a, FocalParams fp, float* __restrict__ partial) {
+    __shared__ float red[256];
+    const int img = blockIdx.y;
+    const int chunk = (a + gridDim.x - 1) / gridDim.x;
+    const int i0 = blockIdx.x * chunk, i1 = min(a, i0 + chunk);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};  // focal, npos, loc_sum, nloc
+    for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
+        const long long o = ((long long)img * a + i) * 4;
+        const float4 y = ld4(yl + o), p = ld4(pl + o);
+        const AnchorTerms t = anchor_terms<false>(y, p, ld4(yb + o), ld4(pb + o));
+        acc[0] += focal_term(y.x, p.x, fp.alpha[0], fp.gamma) + focal_term(y.y, p.y, fp.alpha[1], fp.gamma) +
+                  focal_term(y.z, p.z, fp.alpha[2], fp.gamma) + focal_term(y.w, p.w, fp.alpha[3], fp.gamma);
+        acc[1] += t.not_bg;
+        acc[2] += t.sl1 * t.loc_nb;
+        acc[3] += t.loc_nb;
+    }
+    block_sum<4>(acc, red);
+    if (threadIdx.x == 0) {
+        float* row = partial + ((long long)img * gridDim.x + blockIdx.x) * 4;
+        row[0] = acc[0]; row[1] = acc[1]; row[2] = acc[2]; row[3] = acc[3];
+    }
+}
+
+// per-image totals in fixed order, and the two losses from them
+__global__ void focal_fold_kernel(const float* __restrict__ partial, int nblk, int b, float* __restrict__ img_stats,
+                                  float* __restrict__ conf_loss, float* __restrict__ loc_loss) {
+    const int img = blockIdx.x * blockDim.x + threadIdx.x;
+    if (img >= b) return;
+    float s[4];
+    for (int k = 0; k < 4; ++k) {
+        s[k] = 0.f;
+        for (int q = 0; q < nblk; ++q) s[k] += partial[((long long)img * nblk + q) * 4 + k];
+        img_stats[img * 4 + k] = s[k];
+    }
+    if (conf_loss) conf_loss[img] = s[0] / fmaxf(s[1], 1.f);
+    if (loc_loss) loc_loss[img] = s[2] / fmaxf(s[3], 1.f);
+}
+
+// pass 2: gradients.  Through the softmax: dlogit_j = scale_i p_j (g_j - sum_k p_k g_k), scale_i = conf_scale / max(npos_i, 1)
+__global__ void __launch_bounds__(256) focal_grad_kernel(const float* __restrict__ yl, const float* __restrict__ pl, const float* __restrict__ yb,
+                                                         const float* __restrict__ pb, int a, FocalParams fp, const float* __restrict__ img_stats,
+                                                         float conf_scale, float loc_scale, float* __restrict__ d_logits,
+                                                         float* __restrict__ d_boxes) {
+    const int img = blockIdx.y;
+    const int chunk = (a + gridDim.x - 1) / gridDim.x;
+    const int i0 = blockIdx.x * chunk, i1 = min(a, i0 + chunk);
+    const float sc = conf_scale / fmaxf(img_stats[img * 4 + 1], 1.f);
+    const float inv_loc = 1.f / fmaxf(img_stats[img * 4 + 3], 1.f);
+    for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
+        const long long o = ((long long)img * a + i) * 4;
+        if (d_logits) {
+            const float4 y = ld4(yl + o), p = ld4(pl + o);
+            const float4 pg = make_float4(p.x * focal_grad(y.x, p.x, fp.alpha[0], fp.gamma), p.y * focal_grad(y.y, p.y, fp.alpha[1], fp.gamma),
+                                          p.z * focal_grad(y.z, p.z, fp.alpha[2], fp.gamma), p.w * focal_grad(y.w, p.w, fp.alpha[3], fp.gamma));
+            const float tot = pg.x + pg.y + pg.z + pg.w;
+            st4(d_logits + o, make_float4(sc * (pg.x - p.x * tot), sc * (pg.y - p.y * tot), sc * (pg.z - p.z * tot), sc * (pg.w - p.w * tot)));
+        }
+        if (d_boxes) {
+            const float4 ybx = ld4(yb + o), pbx = ld4(pb + o);
+            st4(d_boxes + o, sl1_grad(has_box(ybx) * inv_loc * loc_scale, ybx, pbx));
+        }
+    }
 }
 
 // ---- dice / dice_square: per image (intersection_c, total_c) over the pixels
@@ -329,24 +429,9 @@ __global__ void dice_finish_kernel(const float* __restrict__ partial, int nblk, 
     loss[img] = l;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ssdseg_topk_mask(ssdseg_ctx* ctx, const float* values, int n, int k, uint8_t* mask) {
-    SSDSEG_ARG(ctx != nullptr, 1);
-    SSDSEG_ARG(values != nullptr, 2);
-    SSDSEG_ARG(n > 0, 3);
-    SSDSEG_ARG(k >= 0, 4);
-    SSDSEG_ARG(mask != nullptr, 5);
-    void* ws;
-    int rc = ssdseg_workspace(ctx, sizeof(TopkState), &ws);
-    if (rc) return rc;
-    return topk_mask_launch(ctx, values, n, k, nullptr, (TopkState*)ws, mask);
-}
-
-int ssdseg_det_loss(ssdseg_ctx* ctx, const float* y_labels, const float* p_labels, const float* y_boxes, const float* p_boxes, int b,
-                    int a, int c, float loss_scale, float* conf_loss, float* loc_loss, float* d_logits, float* d_boxes,
+// the mined confidence loss + localization loss: both public entries (one scale / two scales) launch through here
+int det_loss_launch(ssdseg_ctx* ctx, const float* y_labels, const float* p_labels, const float* y_boxes, const float* p_boxes, int b, int a,
+                    int c, float conf_scale, float loc_scale, float* conf_loss, float* loc_loss, float* d_logits, float* d_boxes,
                     uint8_t* keep_mask) {
     SSDSEG_ARG(ctx != nullptr, 1);
     SSDSEG_ARG(y_labels && p_labels && y_boxes && p_boxes, 2);
@@ -378,11 +463,79 @@ int ssdseg_det_loss(ssdseg_ctx* ctx, const float* y_labels, const float* p_label
     rc = topk_mask_launch(ctx, bgval, (int)n, 0, (const int*)counts, (TopkState*)(base + o_tk), mask);
     if (rc) return rc;
     SSDSEG_LAUNCH(ctx, pass_bytes + 32.0 * n, 0.0, det_final_kernel, dim3(BPI, b), dim3(256), 0, y_labels, p_labels, y_boxes, p_boxes, a, mask,
-                  img_stats, loss_scale, d_logits, d_boxes, partial2);
+                  img_stats, conf_scale, loc_scale, d_logits, d_boxes, partial2);
     SSDSEG_LAUNCH_CHECK();
     SSDSEG_LAUNCH(ctx, 0.0, 0.0, det_finish_kernel, dim3(cdiv(b, 64)), dim3(64), 0, img_stats, partial2, BPI, b, conf_loss, loc_loss);
     SSDSEG_LAUNCH_CHECK();
     if (keep_mask) SSDSEG_HIP(hipMemcpyAsync(keep_mask, mask, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ssdseg_topk_mask(ssdseg_ctx* ctx, const float* values, int n, int k, uint8_t* mask) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    SSDSEG_ARG(values != nullptr, 2);
+    SSDSEG_ARG(n > 0, 3);
+    SSDSEG_ARG(k >= 0, 4);
+    SSDSEG_ARG(mask != nullptr, 5);
+    void* ws;
+    int rc = ssdseg_workspace(ctx, sizeof(TopkState), &ws);
+    if (rc) return rc;
+    return topk_mask_launch(ctx, values, n, k, nullptr, (TopkState*)ws, mask);
+}
+
+int ssdseg_det_loss(ssdseg_ctx* ctx, const float* y_labels, const float* p_labels, const float* y_boxes, const float* p_boxes, int b,
+                    int a, int c, float loss_scale, float* conf_loss, float* loc_loss, float* d_logits, float* d_boxes,
+                    uint8_t* keep_mask) {
+    return det_loss_launch(ctx, y_labels, p_labels, y_boxes, p_boxes, b, a, c, loss_scale, loss_scale, conf_loss, loc_loss, d_logits, d_boxes,
+                           keep_mask);
+}
+
+int ssdseg_det_loss_scaled(ssdseg_ctx* ctx, const float* y_labels, const float* p_labels, const float* y_boxes, const float* p_boxes, int b,
+                           int a, int c, float conf_scale, float loc_scale, float* conf_loss, float* loc_loss, float* d_logits,
+                           float* d_boxes, uint8_t* keep_mask) {
+    return det_loss_launch(ctx, y_labels, p_labels, y_boxes, p_boxes, b, a, c, conf_scale, loc_scale, conf_loss, loc_loss, d_logits, d_boxes,
+                           keep_mask);
+}
+
+int ssdseg_det_loss_focal(ssdseg_ctx* ctx, const float* y_labels, const float* p_labels, const float* y_boxes, const float* p_boxes, int b,
+                          int a, int c, const float* alpha4_host, float gamma, float conf_scale, float loc_scale, float* conf_loss,
+                          float* loc_loss, float* d_logits, float* d_boxes) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    SSDSEG_ARG(y_labels && p_labels && y_boxes && p_boxes, 2);
+    SSDSEG_ARG(b > 0, 6);
+    SSDSEG_ARG(a > 0, 7);
+    SSDSEG_ARG(c == 4, 8);
+    const long long n = (long long)b * a;
+    SSDSEG_ARG(n < (1LL << 30), 6);
+    SSDSEG_ARG(alpha4_host != nullptr, 9);
+    FocalParams fp;
+    for (int k = 0; k < 4; ++k) {
+        SSDSEG_ARG(std::isfinite(alpha4_host[k]) && alpha4_host[k] >= 0.f, 9);
+        fp.alpha[k] = alpha4_host[k];
+    }
+    SSDSEG_ARG(std::isfinite(gamma) && gamma >= 0.f, 10);
+    fp.gamma = gamma;
+    // workspace: partial[b][BPI][4] | img_stats[b][4]; every word of both is written before it is read
+    const size_t o_stats = (size_t)b * BPI * 16, total = o_stats + (size_t)b * 16;
+    void* ws;
+    int rc = ssdseg_workspace(ctx, total, &ws);
+    if (rc) return rc;
+    float* partial = (float*)ws;
+    float* img_stats = (float*)((char*)ws + o_stats);
+    const double pass_bytes = 64.0 * n;
+    SSDSEG_LAUNCH(ctx, pass_bytes, 0.0, focal_prep_kernel, dim3(BPI, b), dim3(256), 0, y_labels, p_labels, y_boxes, p_boxes, a, fp, partial);
+    SSDSEG_LAUNCH_CHECK();
+    SSDSEG_LAUNCH(ctx, 0.0, 0.0, focal_fold_kernel, dim3(cdiv(b, 64)), dim3(64), 0, partial, BPI, b, img_stats, conf_loss, loc_loss);
+    SSDSEG_LAUNCH_CHECK();
+    if (d_logits || d_boxes) {
+        SSDSEG_LAUNCH(ctx, (d_logits ? 48.0 : 0.0) * n + (d_boxes ? 48.0 : 0.0) * n, 0.0, focal_grad_kernel, dim3(BPI, b), dim3(256), 0, y_labels,
+                      p_labels, y_boxes, p_boxes, a, fp, img_stats, conf_scale, loc_scale, d_logits, d_boxes);
+        SSDSEG_LAUNCH_CHECK();
+    }
     return 0;
 }
 

@@ -632,8 +632,10 @@ class SoftmaxRowsOp(Op):
 
 
 class DetLossOp(Op):
-    """confidence + localization losses; the gradients w.r.t. the pre-softmax logits / box offsets are produced in
-    the forward call (fused) and simply stay in the concat stores' gradient buffers."""
+    """confidence (mined or focal) + localization losses; the gradients w.r.t. the pre-softmax logits / box offsets are
+    produced in the forward call (fused), each scaled by its own loss weight / batch, and simply stay in the concat stores'
+    gradient buffers.  Equal weights with the mined loss take the single-scale entry, the step's bits from before the weights
+    could differ."""
 
     def __init__(self, eng, logits: Store, probs: Store, boxes: Store):
         self.e, self.logits, self.probs, self.boxes = eng, logits, probs, boxes
@@ -642,13 +644,20 @@ class DetLossOp(Op):
         self.y_labels = self.y_boxes = None
         self.conf_loss, self.loc_loss = eng.ctx.empty(b), eng.ctx.empty(b)
         self.w_conf = self.w_loc = 1.0
+        self.kind = "mined"                     # "mined": losses.confidence_loss; "focal": losses.focal_confidence_loss(alpha, gamma)
+        self.alpha, self.gamma = None, 0.0
 
     def fwd(self):
         p = self.probs
-        assert self.w_conf == self.w_loc, "per-output loss weights must match for the fused detection loss"
         tr = self.e.training
-        self.e.ctx.call("ssdseg_det_loss", self.y_labels, p.buf, self.y_boxes, self.boxes.buf, p.n, p.h * p.w, p.c, self.w_conf / p.n,
-                        self.conf_loss, self.loc_loss, self.logits.grad if tr else None, self.boxes.grad if tr else None, None)
+        ins = (self.y_labels, p.buf, self.y_boxes, self.boxes.buf, p.n, p.h * p.w, p.c)
+        outs = (self.conf_loss, self.loc_loss, self.logits.grad if tr else None, self.boxes.grad if tr else None)
+        if self.kind == "focal":
+            self.e.ctx.call("ssdseg_det_loss_focal", *ins, self.alpha, self.gamma, self.w_conf / p.n, self.w_loc / p.n, *outs)
+        elif self.w_conf == self.w_loc:
+            self.e.ctx.call("ssdseg_det_loss", *ins, self.w_conf / p.n, *outs, None)
+        else:
+            self.e.ctx.call("ssdseg_det_loss_scaled", *ins, self.w_conf / p.n, self.w_loc / p.n, *outs, None)
 
     def bwd(self):
         self.logits.gwritten = True
@@ -1459,7 +1468,7 @@ class Engine:
                 op.loss = self.ctx.empty(b)
                 op.loss_scale = w / b
                 self._loss_names.append((name, op, "mask"))
-            elif fn is LS.confidence_loss or fn is LS.localization_loss:
+            elif fn is LS.confidence_loss or fn is LS.localization_loss or getattr(fn, "loss_kind", None) == "focal":
                 det = self.loss_ops.get("det")
                 if det is None:
                     labels_v = next(self.vals[id(o)] for o in self.model.outputs if "logits" in self.vals[id(o)].meta)
@@ -1471,7 +1480,12 @@ class Engine:
                     self.loss_ops["det"] = det
                     self._cur_reach = self.DET_OUTPUTS
                     self._emit(det)
-                if fn is LS.confidence_loss:
+                if fn is not LS.localization_loss:
+                    if fn is not LS.confidence_loss:
+                        if "logits" not in v.meta:
+                            raise ValueError(f"loss {fn.__name__} does not fit output {name}: it takes the class probabilities")
+                        det.kind, det.gamma = "focal", float(fn.gamma)
+                        det.alpha = (C.c_float * 4)(*fn.alpha)
                     det.w_conf = w
                     self._loss_names.append((name, det, "conf"))
                 else:

@@ -43,6 +43,40 @@ def confidence_loss(y_true, y_pred):
     return conf.download()
 
 
+def focal_confidence_loss(alpha=(1.0, 1.0, 1.0, 1.0), gamma: float = 2.0) -> Callable:
+    """focal loss on the softmax probabilities of the SSD head (not in the reference): per anchor
+    -sum_c alpha_c y_c (1 - p_c)^gamma log p_c with p clipped like `confidence_loss`, summed over EVERY anchor of an image
+    (no hard-negative mining, so no image depends on the rest of its batch) / max(#non-background anchors, 1).
+    alpha: one weight per class (background first), gamma >= 0; gamma = 0, alpha = 1 is the un-mined cross-entropy."""
+    try:
+        weights = tuple(float(w) for w in alpha)
+    except TypeError:
+        raise ValueError("alpha must hold one weight per class (4)") from None
+    gamma = float(gamma)
+    if len(weights) != 4:
+        raise ValueError(f"alpha must hold one weight per class (4), got {len(weights)}")
+    if not all(np.isfinite(w) and w >= 0.0 for w in weights):
+        raise ValueError(f"alpha must be finite and >= 0, got {weights}")
+    if not (np.isfinite(gamma) and gamma >= 0.0):
+        raise ValueError(f"gamma must be finite and >= 0, got {gamma}")
+
+    def loss_fn(y_true, y_pred):
+        y_true, y_pred = _f32(y_true), _f32(y_pred)
+        b, a, c = y_true.shape
+        ctx = _ctx()
+        zeros = ctx.zeros((b, a, 4))
+        conf = ctx.empty(b)
+        ctx.call("ssdseg_det_loss_focal", ctx.array(y_true), ctx.array(y_pred), zeros, zeros, b, a, c, (C.c_float * 4)(*weights), gamma, 1.0, 1.0,
+                 conf, None, None, None)
+        return conf.download()
+
+    loss_fn.__name__ = "focal_confidence_loss"
+    loss_fn.alpha = weights
+    loss_fn.gamma = gamma
+    loss_fn.loss_kind = "focal"
+    return loss_fn
+
+
 def _mask_loss(mode: int, name: str, kind: str, classes_weights: List[float]) -> Callable:
     weights = tuple(float(w) for w in classes_weights)
 
