@@ -127,8 +127,9 @@ void ssdseg_defer_hold(ssdseg_ctx* ctx, int delta);
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // Environment switches.  Read on every call, never cached: the parity tests flip them inside one process.
-// env_is: the variable is set and starts with `ch`;  env_int: its integer value, `fallback` when unset;
+// env_set: the variable is set, to whatever;  env_is: it is set and starts with `ch`;  env_int: its integer value, `fallback` when unset;
 // env_pick: 1-based position of its value among `values`, 0 when unset or not one of them
+static inline bool env_set(const char* name) { return getenv(name) != nullptr; }
 static inline bool env_is(const char* name, char ch) {
     const char* e = getenv(name);
     return e != nullptr && e[0] == ch;
