@@ -1,0 +1,469 @@
+// Mask head tail of the DeepLabV3+ head, 4 classes, fused: bilinear up-sampling -> Softmax -> weighted cross-entropy or dice
+// (reference blocks.py:128-130 + losses.py:175-303), forward and backward, and the soft-Jaccard metric of the same masks
+// (metrics.py:35-47), which shares the up-sampling, the softmax and the per-image sums.
+#include "lerp_softmax.h"
+
+namespace {
+
+__device__ __forceinline__ float4 up_logits(const float* __restrict__ logits, long long img, int h, int w, int oy, int ox, float ify, float ifx) {
+    const Lerp ly = lerp_of(oy, h, ify), lx = lerp_of(ox, w, ifx);
+    const float* base = logits + img * h * w * 4;
+    const float4 v00 = ld4(base + ((long long)ly.i0 * w + lx.i0) * 4), v01 = ld4(base + ((long long)ly.i0 * w + lx.i1) * 4);
+    const float4 v10 = ld4(base + ((long long)ly.i1 * w + lx.i0) * 4), v11 = ld4(base + ((long long)ly.i1 * w + lx.i1) * 4);
+    return lerp_blend4(v00, v01, v10, v11, lx.f, ly.f);
+}
+__device__ __forceinline__ float clip_log(float p) { return logf(fminf(fmaxf(p, KEPS), 1.f - KEPS)); }
+__device__ __forceinline__ float inside(float p) { return (p >= KEPS && p <= 1.f - KEPS) ? 1.f : 0.f; }
+
+// dL/dp of one pixel.  mode 0: weighted cross-entropy, -w_c y_c / clip(p_c) inside the clip interval, 0 outside (App. B.6);
+// mode 1 / 2: dice / dice_square (reference losses.py:204-216, 250-262): with the per-image sums I_c = sum y p, T_c = sum (y + p)
+// [sum (y^2 + p^2)],  dL/dp_c = A_c y_c + B_c [2 p_c],  A_c = -2 w_c / (T_c + eps),  B_c = w_c (2 I_c + eps) / (T_c + eps)^2
+// (cA, cB: written per image by mask_dice_final_kernel).
+__device__ __forceinline__ float4 mask_dp(int mode, float4 cw, float4 y, float4 pr, float4 cA, float4 cB) {
+    float4 dp;
+    if (mode == 0) {
+        dp.x = -cw.x * y.x / fminf(fmaxf(pr.x, KEPS), 1.f - KEPS) * inside(pr.x);
+        dp.y = -cw.y * y.y / fminf(fmaxf(pr.y, KEPS), 1.f - KEPS) * inside(pr.y);
+        dp.z = -cw.z * y.z / fminf(fmaxf(pr.z, KEPS), 1.f - KEPS) * inside(pr.z);
+        dp.w = -cw.w * y.w / fminf(fmaxf(pr.w, KEPS), 1.f - KEPS) * inside(pr.w);
+    } else {
+        const float4 t = mode == 2 ? make_float4(2.f * pr.x, 2.f * pr.y, 2.f * pr.z, 2.f * pr.w) : f4(1.f);
+        dp.x = fmaf(cA.x, y.x, cB.x * t.x);
+        dp.y = fmaf(cA.y, y.y, cB.y * t.y);
+        dp.z = fmaf(cA.z, y.z, cB.z * t.z);
+        dp.w = fmaf(cA.w, y.w, cB.w * t.w);
+    }
+    return dp;
+}
+
+// dz = softmax'(dL/dp) of the full-resolution pixel (oy, ox) of image img, whose one-hot row is y_pixel: up-sampled logits, softmax,
+// one-hot read, dL/dp
+__device__ __forceinline__ float4 mask_dz(const float* logits, long long img, int h, int w, int oy, int ox, float ify, float ifx,
+                                          const float* y_pixel, int mode, float4 cw, float4 cA, float4 cB) {
+    const float4 pr = softmax4(up_logits(logits, img, h, w, oy, ox, ify, ifx));
+    const float4 y = ld4(y_pixel);
+    const float4 dp = mask_dp(mode, cw, y, pr, cA, cB);
+    const float dot = dp.x * pr.x + dp.y * pr.y + dp.z * pr.z + dp.w * pr.w;
+    return make_float4(pr.x * (dp.x - dot), pr.y * (dp.y - dot), pr.z * (dp.z - dot), pr.w * (dp.w - dot));
+}
+
+// one pixel's terms of the eight per-image sums of the dice losses and of the soft Jaccard: s[c] = I_c = sum y_c p_c,
+// s[4 + c] = T_c = sum (y_c + p_c)  [squared: sum (y_c^2 + p_c^2)]
+__device__ __forceinline__ void overlap_sums_add(float (&s)[8], float4 y, float4 pr, bool squared) {
+    s[0] = fmaf(y.x, pr.x, s[0]); s[1] = fmaf(y.y, pr.y, s[1]); s[2] = fmaf(y.z, pr.z, s[2]); s[3] = fmaf(y.w, pr.w, s[3]);
+    if (squared) {
+        s[4] += fmaf(y.x, y.x, pr.x * pr.x); s[5] += fmaf(y.y, y.y, pr.y * pr.y); s[6] += fmaf(y.z, y.z, pr.z * pr.z); s[7] += fmaf(y.w, y.w, pr.w * pr.w);
+    } else {
+        s[4] += y.x + pr.x; s[5] += y.y + pr.y; s[6] += y.z + pr.z; s[7] += y.w + pr.w;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ forward
+// grid (blocks_per_image, n); partial[n][blocks_per_image] per-image loss partials
+__global__ void __launch_bounds__(256) mask_head_fwd_kernel(const float* __restrict__ logits, int h, int w, int fy, int fx,
+                                                            const float* __restrict__ y_true, float4 cw, float* __restrict__ prob,
+                                                            float* __restrict__ partial) {
+    __shared__ float red[1][256];
+    const int ho = h * fy, wo = w * fx;
+    const long long npix = (long long)ho * wo;
+    const long long img = blockIdx.y;
+    const float ify = 1.f / (float)fy, ifx = 1.f / (float)fx;
+    float loss = 0.f;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+        const int ox = (int)(p % wo), oy = (int)(p / wo);
+        const float4 pr = softmax4(up_logits(logits, img, h, w, oy, ox, ify, ifx));
+        const long long off = (img * npix + p) * 4;
+        if (prob) st4(prob + off, pr);
+        if (y_true) {
+            const float4 y = ld4(y_true + off);
+            loss -= cw.x * y.x * clip_log(pr.x) + cw.y * y.y * clip_log(pr.y) + cw.z * y.z * clip_log(pr.z) + cw.w * y.w * clip_log(pr.w);
+        }
+    }
+    if (partial) {
+        const float v[1] = {loss};
+        block_sum256(v, red);
+        if (threadIdx.x == 0) partial[img * gridDim.x + blockIdx.x] = red[0][0];
+    }
+}
+
+__global__ void mask_loss_final_kernel(const float* __restrict__ partial, int nblk, float* __restrict__ loss, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int b = 0; b < nblk; ++b) s += (double)partial[(long long)i * nblk + b];
+    loss[i] = (float)s;
+}
+
+// dice / dice_square forward: probabilities (optional) and per-block partial sums (I_c, T_c); grid (blocks_per_image, n),
+// partial[n][blocks_per_image][8]
+__global__ void __launch_bounds__(256) mask_head_fwd_dice_kernel(const float* __restrict__ logits, int h, int w, int fy, int fx,
+                                                                 const float* __restrict__ y_true, int squared, float* __restrict__ prob,
+                                                                 float* __restrict__ partial) {
+    __shared__ float red[8][256];
+    const int ho = h * fy, wo = w * fx;
+    const long long npix = (long long)ho * wo;
+    const long long img = blockIdx.y;
+    const float ify = 1.f / (float)fy, ifx = 1.f / (float)fx;
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+        const int ox = (int)(p % wo), oy = (int)(p / wo);
+        const float4 pr = softmax4(up_logits(logits, img, h, w, oy, ox, ify, ifx));
+        const long long off = (img * npix + p) * 4;
+        if (prob) st4(prob + off, pr);
+        overlap_sums_add(s, ld4(y_true + off), pr, squared);
+    }
+    block_sum256(s, red);
+    const int t = threadIdx.x;
+    if (t < 8) partial[(img * gridDim.x + blockIdx.x) * 8 + t] = red[t][0];
+}
+
+// per image: I_c, T_c (partials summed in index order, double), the loss, and the backward coefficients coef[img] = (A_0..3, B_0..3)
+__global__ void mask_dice_final_kernel(const float* __restrict__ partial, int nblk, int n, float4 cw, float* __restrict__ loss,
+                                       float* __restrict__ coef) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int b = 0; b < nblk; ++b)
+#pragma unroll
+        for (int v = 0; v < 8; ++v) s[v] += (double)partial[((long long)i * nblk + b) * 8 + v];
+    const double w[4] = {cw.x, cw.y, cw.z, cw.w};
+    const double eps = (double)KEPS;
+    double l = 0.0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const double den = s[4 + c] + eps, num = 2.0 * s[c] + eps;
+        l += w[c] * (1.0 - num / den);
+        if (coef != nullptr) {
+            coef[i * 8 + c] = (float)(-2.0 * w[c] / den);
+            coef[i * 8 + 4 + c] = (float)(w[c] * num / (den * den));
+        }
+    }
+    if (loss != nullptr) loss[i] = (float)l;
+}
+
+// ------------------------------------------------------------------------------------------------ backward
+// dlogits(low res) = sum over the full-res pixels that interpolate from it of weight * dz, dz = softmax'(dL/dp)
+__global__ void __launch_bounds__(256) mask_head_bwd_kernel(const float* __restrict__ logits, int n, int h, int w, int fy, int fx,
+                                                            const float* __restrict__ y_true, float4 cw, float loss_scale,
+                                                            float* __restrict__ dlogits, int mode, const float* __restrict__ coef) {
+    const int ho = h * fy, wo = w * fx;
+    const long long total = (long long)n * h * w;
+    const float ify = 1.f / (float)fy, ifx = 1.f / (float)fx;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int ix = (int)(i % w);
+        const int iy = (int)((i / w) % h);
+        const long long img = i / ((long long)w * h);
+        const LerpWindow win = lerp_window(iy, ix, h, w, fy, fx);
+        float4 acc = f4(0.f);
+        const float4 cA = mode != 0 ? ld4(coef + img * 8) : f4(0.f), cB = mode != 0 ? ld4(coef + img * 8 + 4) : f4(0.f);
+        for (int oy = win.oy0; oy <= win.oy1; ++oy) {
+            const float wy = lerp_weight(oy, iy, h, ify);
+            if (wy == 0.f) continue;
+            for (int ox = win.ox0; ox <= win.ox1; ++ox) {
+                const float wx = lerp_weight(ox, ix, w, ifx);
+                if (wx == 0.f) continue;
+                axpy4(acc, wy * wx * loss_scale, mask_dz(logits, img, h, w, oy, ox, ify, ifx, y_true + ((img * ho + oy) * wo + ox) * 4, mode, cw, cA, cB));
+            }
+        }
+        st4(dlogits + i * 4, acc);
+    }
+}
+
+// The tile kernels below form the same sum with each full-resolution pixel's dz computed ONCE per block instead of once per
+// contributing low-resolution pixel (x16 up-sampling area: every dz has up to four takers, and the kernel above re-does the bilinear
+// gather, the softmax and the one-hot read for each of them: 0.31 ms at 480x640, batch 32).  A block owns a TL x TL tile of
+// low-resolution pixels and first writes the dz of the R x R full-resolution pixels that can reach them into LDS, R = TL*F + F:
+// low-res pixel i takes weight from [i*F - F/2, i*F + F + F/2 - 1] (lerp_window), so a tile of TL pixels draws from TL*F + F
+// indices, starting at i0*F - F/2.  This is that phase, for a block of NT threads; it ends with the barrier.
+struct MaskTile {
+    long long img;
+    int iy0, ix0;      // first low-resolution pixel of the tile
+    int oyb, oxb;      // full-resolution pixel of dz[0]
+};
+template <int F, int TL, int NT>
+__device__ __forceinline__ MaskTile mask_dz_fill(float4* dz, const float* logits, int h, int w, const float* y_true, float4 cw, int mode,
+                                                 const float* coef) {
+    constexpr int R = TL * F + F;
+    const int ho = h * F, wo = w * F;
+    const float inv = 1.f / (float)F;
+    const int tiles_x = (w + TL - 1) / TL, tiles_y = (h + TL - 1) / TL;
+    int b = blockIdx.x;
+    const int tx = b % tiles_x; b /= tiles_x;
+    const int ty = b % tiles_y;
+    MaskTile t;
+    t.img = b / tiles_y;
+    t.iy0 = ty * TL; t.ix0 = tx * TL;
+    t.oyb = t.iy0 * F - F / 2; t.oxb = t.ix0 * F - F / 2;
+    const float4 cA = mode != 0 ? ld4(coef + t.img * 8) : f4(0.f), cB = mode != 0 ? ld4(coef + t.img * 8 + 4) : f4(0.f);
+    for (int i = threadIdx.x; i < R * R; i += NT) {
+        const int ry = i / R, rx = i - ry * R;
+        const int oy = t.oyb + ry, ox = t.oxb + rx;
+        float4 v = f4(0.f);
+        if (oy >= 0 && oy < ho && ox >= 0 && ox < wo)
+            v = mask_dz(logits, t.img, h, w, oy, ox, inv, inv, y_true + ((t.img * ho + oy) * wo + ox) * 4, mode, cw, cA, cB);
+        dz[i] = v;
+    }
+    __syncthreads();
+    return t;
+}
+
+// x4: after the dz phase every thread gathers the window of its low-resolution pixel from LDS.  Each dz is the same expression and
+// the window is walked in the same (oy, ox) order as in mask_head_bwd_kernel: results are bit-identical.
+template <int F, int TL>
+__global__ void __launch_bounds__(TL * TL) mask_head_bwd_tile_kernel(const float* __restrict__ logits, int n, int h, int w,
+                                                                       const float* __restrict__ y_true, float4 cw, float loss_scale,
+                                                                       float* __restrict__ dlogits, int mode, const float* __restrict__ coef) {
+    constexpr int R = TL * F + F;
+    extern __shared__ float4 dz[];                    // [R][R]
+    const MaskTile tile = mask_dz_fill<F, TL, TL * TL>(dz, logits, h, w, y_true, cw, mode, coef);
+    const float inv = 1.f / (float)F;
+    const int ly = threadIdx.x / TL, lx = threadIdx.x - ly * TL;
+    const int iy = tile.iy0 + ly, ix = tile.ix0 + lx;
+    if (iy >= h || ix >= w) return;
+    const LerpWindow win = lerp_window(iy, ix, h, w, F, F);
+    // the column weights of the window once per thread, not once per (row, column) -- the same lerp_weight values, the same products and
+    // the same summation order (rows, then columns, zero weights skipped): bit-identical, ~130 weight evaluations per thread less
+    constexpr int WMAX = lerp_window_max(F);
+    float wxs[WMAX];
+#pragma unroll
+    for (int k = 0; k < WMAX; ++k) wxs[k] = (win.ox0 + k <= win.ox1) ? lerp_weight(win.ox0 + k, ix, w, inv) : 0.f;
+    float4 acc = f4(0.f);
+    for (int oy = win.oy0; oy <= win.oy1; ++oy) {
+        const float wy = lerp_weight(oy, iy, h, inv);
+        if (wy == 0.f) continue;
+        const float4* drow = dz + (oy - tile.oyb) * R + (win.ox0 - tile.oxb);
+#pragma unroll
+        for (int k = 0; k < WMAX; ++k) {
+            const float wx = wxs[k];
+            if (wx == 0.f) continue;
+            axpy4(acc, wy * wx * loss_scale, drow[k]);
+        }
+    }
+    st4(dlogits + ((tile.img * h + iy) * w + ix) * 4, acc);
+}
+
+// Larger factors (x8: ShuffleNetV2's 60 x 80 logits): a window holds (2F + F/2)^2 full-resolution pixels, so the gather is split over
+// PARTS threads per low-resolution pixel (interleaved rows, partials folded in part order: deterministic, but not the summation
+// order of the one-thread kernel) and all TL^2 * PARTS threads share the dz phase.
+template <int F, int TL, int PARTS>
+__global__ void __launch_bounds__(TL * TL * PARTS) mask_head_bwd_tile_split_kernel(const float* __restrict__ logits, int n, int h, int w,
+                                                                                     const float* __restrict__ y_true, float4 cw, float loss_scale,
+                                                                                     float* __restrict__ dlogits, int mode, const float* __restrict__ coef) {
+    constexpr int R = TL * F + F;
+    extern __shared__ float4 dz[];                    // [R][R] + [PARTS][TL * TL]
+    float4* red = dz + R * R;
+    const MaskTile tile = mask_dz_fill<F, TL, TL * TL * PARTS>(dz, logits, h, w, y_true, cw, mode, coef);
+    const float inv = 1.f / (float)F;
+    const int pix = threadIdx.x % (TL * TL), part = threadIdx.x / (TL * TL);
+    const int ly = pix / TL, lx = pix - ly * TL;
+    const int iy = tile.iy0 + ly, ix = tile.ix0 + lx;
+    const bool live = iy < h && ix < w;
+    const LerpWindow win = lerp_window(iy, ix, h, w, F, F);      // (in front of the branch: measured 2 % faster than inside it)
+    float4 acc = f4(0.f);
+    if (live) {
+        for (int oy = win.oy0 + part; oy <= win.oy1; oy += PARTS) {
+            const float wy = lerp_weight(oy, iy, h, inv);
+            if (wy == 0.f) continue;
+            for (int ox = win.ox0; ox <= win.ox1; ++ox) {
+                const float wx = lerp_weight(ox, ix, w, inv);
+                if (wx == 0.f) continue;
+                axpy4(acc, wy * wx * loss_scale, dz[(oy - tile.oyb) * R + (ox - tile.oxb)]);
+            }
+        }
+    }
+    red[part * TL * TL + pix] = acc;
+    __syncthreads();
+    if (part == 0 && live) {
+        float4 s = red[pix];
+#pragma unroll
+        for (int q = 1; q < PARTS; ++q) add4(s, red[q * TL * TL + pix]);
+        st4(dlogits + ((tile.img * h + iy) * w + ix) * 4, s);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ soft Jaccard metric
+// (reference metrics.py:35-47; per-image values, Keras averages them): per image and class  inter = sum t*p,  total = sum (t + p)
+// over the full-resolution pixels; p = softmax(upsampled logits) when FROM_LOGITS (the training path never stores the
+// probabilities) or the given probabilities.  Two-level reduction in fixed order.  grid (nblk, n) -> partial[n][nblk][8]
+template <bool FROM_LOGITS>
+__global__ void __launch_bounds__(256) mask_iou_partial_kernel(const float* __restrict__ src, int h, int w, int fy, int fx,
+                                                               const float* __restrict__ y_true, float* __restrict__ partial) {
+    __shared__ float red[1][256];
+    const int ho = h * fy, wo = w * fx;
+    const long long npix = (long long)ho * wo;
+    const int img = blockIdx.y;
+    const float ify = 1.f / (float)fy, ifx = 1.f / (float)fx;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < npix; i += (long long)gridDim.x * 256) {
+        const int oy = (int)(i / wo), ox = (int)(i - (long long)oy * wo);
+        float4 pr;
+        if (FROM_LOGITS) pr = softmax4(up_logits(src, img, h, w, oy, ox, ify, ifx));
+        else pr = ld4(src + ((long long)img * npix + i) * 4);
+        overlap_sums_add(acc, ld4(y_true + ((long long)img * npix + i) * 4), pr, false);
+    }
+    for (int k = 0; k < 8; ++k) {       // one value per pass: 1 KiB of LDS
+        __syncthreads();
+        const float v[1] = {acc[k]};
+        block_sum256(v, red);
+        if (threadIdx.x == 0) partial[((long long)img * gridDim.x + blockIdx.x) * 8 + k] = red[0][0];
+    }
+}
+__global__ void mask_iou_finish_kernel(const float* __restrict__ partial, int nblk, int n, float4 cw, float* __restrict__ out) {
+    const int img = blockIdx.x * blockDim.x + threadIdx.x;
+    if (img >= n) return;
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < nblk; ++q)
+        for (int k = 0; k < 8; ++k) s[k] += partial[((long long)img * nblk + q) * 8 + k];
+    const float w[4] = {cw.x, cw.y, cw.z, cw.w};
+    float m = 0.f;
+    for (int c = 0; c < 4; ++c) m += s[c] / (s[4 + c] - s[c] + KEPS) * w[c];   // metrics.py:41-45
+    out[img] = m;
+}
+
+// ------------------------------------------------------------------------------------------------ host
+// blocks per image of a two-level sum over npix full-resolution pixels: eight pixels per thread, at most `cap`
+int partial_blocks(long long npix, int cap) {
+    const long long nblk = (npix + 256 * 8 - 1) / (256 * 8);
+    return (int)(nblk > cap ? cap : (nblk < 1 ? 1 : nblk));
+}
+
+// launches Kernel with `lds` bytes of dynamic LDS, more than the default limit: raised on the kernel's first launch (one flag per
+// kernel: Kernel is a template argument).  `name`: what the launch leaves in the timing registry.
+template <auto Kernel, typename... Args>
+int launch_with_lds(ssdseg_ctx* ctx, const char* name, double bytes, long long blocks, int threads, size_t lds, Args... args) {
+    static bool configured = false;
+    if (!configured) {
+        SSDSEG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        configured = true;
+    }
+    SSDSEG_LAUNCH_NAMED(ctx, name, bytes, 0.0, Kernel, dim3((unsigned)blocks), dim3(threads), lds, args...);
+    SSDSEG_LAUNCH_CHECK();
+    return 0;
+}
+
+// mode 0: cross-entropy (cwh: the class weights); 1 / 2: dice / dice_square (coef: mask_dice_final_kernel's)
+int mask_head_bwd_launch(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int fy, int fx, const float* y_true, const float* cwh,
+                         float loss_scale, float* dlogits, int mode, const float* coef) {
+    const double bytes = 16.0 * n * h * fy * wdt * fx;
+    const float4 cw = f4_of(cwh);
+    const bool tiles = env_pick("SSDSEG_MASK_BWD", {"gather"}) == 0;      // "gather": the one-thread-per-pixel kernel (A/B runs, parity tests)
+    if (tiles && fy == 4 && fx == 4) {
+        constexpr int F = 4, TL = 16, R = TL * F + F;
+        return launch_with_lds<mask_head_bwd_tile_kernel<F, TL>>(ctx, "(mask_head_bwd_tile_kernel<F, TL>)", bytes, (long long)n * cdiv(h, TL) * cdiv(wdt, TL),
+                                                                  TL * TL, R * R * sizeof(float4), logits, n, h, wdt, y_true, cw, loss_scale, dlogits, mode, coef);
+    }
+    if (tiles && fy == 8 && fx == 8) {
+        constexpr int F = 8, TL = 8, PARTS = 4, R = TL * F + F;
+        return launch_with_lds<mask_head_bwd_tile_split_kernel<F, TL, PARTS>>(ctx, "(mask_head_bwd_tile_split_kernel<F, TL, PARTS>)", bytes,
+                                                                               (long long)n * cdiv(h, TL) * cdiv(wdt, TL), TL * TL * PARTS,
+                                                                               (size_t)(R * R + PARTS * TL * TL) * sizeof(float4), logits, n, h, wdt, y_true, cw,
+                                                                               loss_scale, dlogits, mode, coef);
+    }
+    SSDSEG_LAUNCH(ctx, bytes, 0.0, mask_head_bwd_kernel, dim3(ew_blocks((long long)n * h * wdt)), dim3(256), 0, logits, n, h, wdt, fy, fx, y_true, cw,
+                  loss_scale, dlogits, mode, coef);
+    SSDSEG_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+// what the four mask-head entry points check first (a macro: SSDSEG_ARG reports under, and returns from, the entry point's own name)
+#define MASK_HEAD_ARGS()                                                                                       \
+    SSDSEG_ARG(ctx != nullptr, 1);                                                                             \
+    SSDSEG_ARG(logits != nullptr, 2);                                                                          \
+    SSDSEG_ARG(n > 0 && h > 0 && wdt > 0, 3);                                                                  \
+    SSDSEG_ARG(c == 4, 6);   /* the reference itself hard-codes depth 4 (layers.py:204, models.py:250-253) */  \
+    SSDSEG_ARG(fy >= 1 && fx >= 1, 7)
+
+extern "C" {
+
+int ssdseg_mask_head_fwd(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx, const float* y_true,
+                         const float* class_weights_host, float* prob, float* loss) {
+    MASK_HEAD_ARGS();
+    SSDSEG_ARG((loss == nullptr) || (y_true != nullptr && class_weights_host != nullptr), 9);
+    const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+    const long long npix = (long long)h * fy * wdt * fx;
+    const int nblk = partial_blocks(npix, 256);
+    float* partial = nullptr;
+    if (loss) {
+        void* ws;
+        int rc = ssdseg_workspace(ctx, (size_t)n * nblk * sizeof(float), &ws);
+        if (rc) return rc;
+        partial = (float*)ws;
+    }
+    SSDSEG_LAUNCH(ctx, 16.0 * n * npix * ((y_true ? 1 : 0) + (prob ? 1 : 0)), 0.0, mask_head_fwd_kernel, dim3(nblk, n), dim3(256), 0, logits, h,
+                  wdt, fy, fx, loss ? y_true : nullptr, f4_of(loss ? class_weights_host : zero), prob, partial);
+    SSDSEG_LAUNCH_CHECK();
+    if (loss) {
+        SSDSEG_LAUNCH(ctx, 4.0 * n * nblk, 0.0, mask_loss_final_kernel, dim3(cdiv(n, 64)), dim3(64), 0, partial, nblk, loss, n);
+        SSDSEG_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+int ssdseg_mask_head_fwd_dice(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx, const float* y_true,
+                              const float* class_weights_host, int squared, float* prob, float* loss, float* coef) {
+    MASK_HEAD_ARGS();
+    SSDSEG_ARG(y_true != nullptr, 9);
+    SSDSEG_ARG(class_weights_host != nullptr, 10);
+    SSDSEG_ARG(loss != nullptr || coef != nullptr, 13);
+    const long long npix = (long long)h * fy * wdt * fx;
+    const int nblk = partial_blocks(npix, 256);
+    void* ws;
+    int rc = ssdseg_workspace(ctx, (size_t)n * nblk * 8 * sizeof(float), &ws);
+    if (rc) return rc;
+    SSDSEG_LAUNCH(ctx, 16.0 * n * npix * (1 + (prob ? 1 : 0)), 0.0, mask_head_fwd_dice_kernel, dim3(nblk, n), dim3(256), 0, logits, h, wdt, fy, fx,
+                  y_true, squared ? 1 : 0, prob, (float*)ws);
+    SSDSEG_LAUNCH_CHECK();
+    SSDSEG_LAUNCH(ctx, 32.0 * n * nblk, 0.0, mask_dice_final_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (const float*)ws, nblk, n,
+                  f4_of(class_weights_host), loss, coef);
+    SSDSEG_LAUNCH_CHECK();
+    return 0;
+}
+
+int ssdseg_mask_head_bwd_dice(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx, const float* y_true,
+                              const float* coef, int squared, float loss_scale, float* dlogits) {
+    MASK_HEAD_ARGS();
+    SSDSEG_ARG(y_true != nullptr, 9);
+    SSDSEG_ARG(coef != nullptr, 10);
+    SSDSEG_ARG(dlogits != nullptr, 13);
+    const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+    return mask_head_bwd_launch(ctx, logits, n, h, wdt, fy, fx, y_true, zero, loss_scale, dlogits, squared ? 2 : 1, coef);
+}
+
+int ssdseg_mask_head_bwd(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx, const float* y_true,
+                         const float* class_weights_host, float loss_scale, float* dlogits) {
+    MASK_HEAD_ARGS();
+    SSDSEG_ARG(y_true != nullptr, 9);
+    SSDSEG_ARG(class_weights_host != nullptr, 10);
+    SSDSEG_ARG(dlogits != nullptr, 12);
+    return mask_head_bwd_launch(ctx, logits, n, h, wdt, fy, fx, y_true, class_weights_host, loss_scale, dlogits, 0, nullptr);
+}
+
+int ssdseg_metric_mask_iou(ssdseg_ctx* ctx, const float* src, int n, int h, int wdt, int c, int fy, int fx, int from_logits,
+                           const float* y_true, const float* class_weights_host, float* out) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    SSDSEG_ARG(src != nullptr, 2);
+    SSDSEG_ARG(n > 0 && h > 0 && wdt > 0, 3);
+    SSDSEG_ARG(c == 4, 6);
+    SSDSEG_ARG(fy >= 1 && fx >= 1 && (from_logits || (fy == 1 && fx == 1)), 7);
+    SSDSEG_ARG(y_true != nullptr, 10);
+    SSDSEG_ARG(class_weights_host != nullptr, 11);
+    SSDSEG_ARG(out != nullptr, 12);
+    const long long npix = (long long)h * fy * wdt * fx;
+    const int nblk = partial_blocks(npix, 64);
+    void* ws;
+    int rc = ssdseg_workspace(ctx, (size_t)n * nblk * 8 * sizeof(float), &ws);
+    if (rc) return rc;
+    const double bytes = 16.0 * n * npix * (from_logits ? 1.0 : 2.0);
+    if (from_logits)
+        SSDSEG_LAUNCH(ctx, bytes, 0.0, mask_iou_partial_kernel<true>, dim3(nblk, n), dim3(256), 0, src, h, wdt, fy, fx, y_true, (float*)ws);
+    else
+        SSDSEG_LAUNCH(ctx, bytes, 0.0, mask_iou_partial_kernel<false>, dim3(nblk, n), dim3(256), 0, src, h, wdt, fy, fx, y_true, (float*)ws);
+    SSDSEG_LAUNCH_CHECK();
+    SSDSEG_LAUNCH(ctx, 0.0, 0.0, mask_iou_finish_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (const float*)ws, nblk, n, f4_of(class_weights_host), out);
+    SSDSEG_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"
