@@ -344,6 +344,24 @@ int ssdseg_mask_head_fwd_dice(ssdseg_ctx* ctx, const float* logits, int n, int h
                               float* coef);
 int ssdseg_mask_head_bwd_dice(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx,
                               const float* y_true, const float* coef, int squared, float loss_scale, float* dlogits);
+/* The same head trained with the bootstrapped cross-entropy (hard-pixel mining; not in the reference).  Per image, with
+ * l_i = -sum_c w_c y_ic log(clip p_ic) the cross-entropy term of pixel i (float32, the expression ssdseg_mask_head_fwd sums):
+ * thresh = the keep-th largest l of the image (1 <= keep <= H*W, H*W = h*fy * wdt*fx), found by an exact radix select;
+ * pixel i is kept when l_i >= thresh -- EVERY pixel tied with the keep-th value, so kept[img] may exceed keep (no tie-break by
+ * index); loss[img] = sum of the kept l.  keep = H*W is the cross-entropy.  The forward writes pixel_loss [n][H*W] (4 bytes per
+ * pixel) and thresh [n]; the backward reads both back and compares the STORED l with thresh, so its keep decision is the
+ * forward's bit for bit: dlogits = upsample^T(softmax'(dL/dp)) with the cross-entropy's dL/dp for kept pixels and an exact zero
+ * row for dropped ones.  prob, kept, loss may be NULL. */
+int ssdseg_mask_head_fwd_bootstrap(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx,
+                                   const float* y_true, const float* class_weights_host, int keep, float* prob,
+                                   float* pixel_loss, float* thresh, int* kept, float* loss);
+int ssdseg_mask_head_bwd_bootstrap(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx,
+                                   const float* y_true, const float* class_weights_host, const float* pixel_loss,
+                                   const float* thresh, float loss_scale, float* dlogits);
+/* the same loss from given probabilities (API surface: losses.bootstrapped_cross_entropy called directly): y_true, p [n][hw][c],
+ * loss [n] */
+int ssdseg_bootstrap_ce_loss(ssdseg_ctx* ctx, const float* y_true, const float* p, int n, int hw, int c,
+                             const float* class_weights_host, int keep, float* loss);
 /* SSD head plumbing: Reshape(-1, 4) + Concatenate(axis=1) (blocks.py:155; models.py:256,271).  Forward: the activated
  * head tensor of one feature map, in[b][in_img_elems] (channel of element r = r % c), is written to
  * out[b][out_off_elems + r] of a buffer with out_img_elems floats per image.  reverse != 0 copies the other way

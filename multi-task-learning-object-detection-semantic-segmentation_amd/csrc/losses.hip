@@ -8,6 +8,7 @@
 // 32-bit keys and ties are broken by the lower index, which is tf.math.top_k's rule.
 // All float reductions are two-level with a fixed order (no float atomics).
 #include "common.h"
+#include "radix_select.h"
 
 namespace {
 
@@ -17,11 +18,6 @@ constexpr int BPI = 16;  // blocks per image in the per-anchor passes
 __device__ __forceinline__ float clipf(float p) { return fminf(fmaxf(p, KEPS), 1.f - KEPS); }
 __device__ __forceinline__ float logcr(float p) { return (float)log((double)p); }
 __device__ __forceinline__ float insidef(float p) { return (p >= KEPS && p <= 1.f - KEPS) ? 1.f : 0.f; }
-
-__device__ __forceinline__ unsigned order_key(float v) {
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);   // larger float <=> larger unsigned key
-}
 
 template <int NV>
 __device__ __forceinline__ void block_sum(float (&v)[NV], float* red) {
@@ -146,26 +142,9 @@ __device__ __forceinline__ int topk_k(int k_host, const int* __restrict__ counts
     return nbg == 0 ? 0 : min(3 * npos, nbg);
 }
 
-// Every block re-derives the selection from the finished histograms of the earlier passes (256 ints each: cheaper than a
-// one-block kernel between passes): prefix = the top 8*npass bits of the k-th largest key, krem = its rank inside that bucket.
+// the selection so far, from the finished histograms of the earlier passes (radix_select.h)
 __device__ __forceinline__ void topk_select(const TopkState* __restrict__ st, int npass, int k, int* lh, unsigned* s_prefix, int* s_krem) {
-    const int t = threadIdx.x;
-    if (t == 0) { *s_prefix = 0u; *s_krem = k; }
-    for (int p = 0; p < npass; ++p) {
-        __syncthreads();
-        lh[t] = st->hist[p][t];
-        __syncthreads();
-        if (t == 0) {
-            int krem = *s_krem, bin = 255;
-            for (; bin > 0; --bin) {
-                if (lh[bin] >= krem) break;
-                krem -= lh[bin];
-            }
-            *s_prefix |= (unsigned)bin << (24 - 8 * p);
-            *s_krem = krem;
-        }
-    }
-    __syncthreads();
+    radix_select_prefix(st->hist, npass, k, lh, s_prefix, s_krem);
 }
 
 __global__ void __launch_bounds__(TK_THREADS) topk_hist_kernel(const float* __restrict__ v, int n, int k_host, const int* __restrict__ counts,

@@ -1,7 +1,9 @@
 // Mask head tail of the DeepLabV3+ head, 4 classes, fused: bilinear up-sampling -> Softmax -> weighted cross-entropy or dice
 // (reference blocks.py:128-130 + losses.py:175-303), forward and backward, and the soft-Jaccard metric of the same masks
-// (metrics.py:35-47), which shares the up-sampling, the softmax and the per-image sums.
+// (metrics.py:35-47), which shares the up-sampling, the softmax and the per-image sums.  Not in the reference: the bootstrapped
+// cross-entropy (hard-pixel mining), which keeps the `keep` largest per-pixel cross-entropy terms of every image.
 #include "lerp_softmax.h"
+#include "radix_select.h"
 
 namespace {
 
@@ -14,14 +16,20 @@ __device__ __forceinline__ float4 up_logits(const float* __restrict__ logits, lo
 }
 __device__ __forceinline__ float clip_log(float p) { return logf(fminf(fmaxf(p, KEPS), 1.f - KEPS)); }
 __device__ __forceinline__ float inside(float p) { return (p >= KEPS && p <= 1.f - KEPS) ? 1.f : 0.f; }
+// sum_c w_c y_c clip_log(p_c) of one pixel, the expression mask_head_fwd_kernel subtracts: negated, the bootstrapped loss's key
+__device__ __forceinline__ float ce_term(float4 cw, float4 y, float4 pr) {
+    return cw.x * y.x * clip_log(pr.x) + cw.y * y.y * clip_log(pr.y) + cw.z * y.z * clip_log(pr.z) + cw.w * y.w * clip_log(pr.w);
+}
 
 // dL/dp of one pixel.  mode 0: weighted cross-entropy, -w_c y_c / clip(p_c) inside the clip interval, 0 outside (App. B.6);
 // mode 1 / 2: dice / dice_square (reference losses.py:204-216, 250-262): with the per-image sums I_c = sum y p, T_c = sum (y + p)
 // [sum (y^2 + p^2)],  dL/dp_c = A_c y_c + B_c [2 p_c],  A_c = -2 w_c / (T_c + eps),  B_c = w_c (2 I_c + eps) / (T_c + eps)^2
-// (cA, cB: written per image by mask_dice_final_kernel).
+// (cA, cB: written per image by mask_dice_final_kernel);  mode 3: bootstrapped cross-entropy, mode 0's expression (mask_dz selects
+// the kept pixels).
+constexpr int MASK_BOOTSTRAP = 3;
 __device__ __forceinline__ float4 mask_dp(int mode, float4 cw, float4 y, float4 pr, float4 cA, float4 cB) {
     float4 dp;
-    if (mode == 0) {
+    if (mode == 0 || mode == MASK_BOOTSTRAP) {
         dp.x = -cw.x * y.x / fminf(fmaxf(pr.x, KEPS), 1.f - KEPS) * inside(pr.x);
         dp.y = -cw.y * y.y / fminf(fmaxf(pr.y, KEPS), 1.f - KEPS) * inside(pr.y);
         dp.z = -cw.z * y.z / fminf(fmaxf(pr.z, KEPS), 1.f - KEPS) * inside(pr.z);
@@ -37,12 +45,16 @@ __device__ __forceinline__ float4 mask_dp(int mode, float4 cw, float4 y, float4 
 }
 
 // dz = softmax'(dL/dp) of the full-resolution pixel (oy, ox) of image img, whose one-hot row is y_pixel: up-sampled logits, softmax,
-// one-hot read, dL/dp
+// one-hot read, dL/dp.  Bootstrapped mode: l_pixel is the pixel's loss as the forward STORED it and thr its image's threshold; the
+// keep decision is the forward's comparison on the forward's bits (a recomputed loss would be at the mercy of contraction), and a
+// dropped pixel's dL/dp is selected to an exact zero row, so its dz is +0.
 __device__ __forceinline__ float4 mask_dz(const float* logits, long long img, int h, int w, int oy, int ox, float ify, float ifx,
-                                          const float* y_pixel, int mode, float4 cw, float4 cA, float4 cB) {
+                                          const float* y_pixel, int mode, float4 cw, float4 cA, float4 cB, const float* l_pixel, float thr) {
     const float4 pr = softmax4(up_logits(logits, img, h, w, oy, ox, ify, ifx));
     const float4 y = ld4(y_pixel);
-    const float4 dp = mask_dp(mode, cw, y, pr, cA, cB);
+    float4 dp = mask_dp(mode, cw, y, pr, cA, cB);
+    const bool kept = mode != MASK_BOOTSTRAP || *l_pixel >= thr;
+    dp = kept ? dp : f4(0.f);
     const float dot = dp.x * pr.x + dp.y * pr.y + dp.z * pr.z + dp.w * pr.w;
     return make_float4(pr.x * (dp.x - dot), pr.y * (dp.y - dot), pr.z * (dp.z - dot), pr.w * (dp.w - dot));
 }
@@ -92,6 +104,116 @@ __global__ void mask_loss_final_kernel(const float* __restrict__ partial, int nb
     double s = 0.0;
     for (int b = 0; b < nblk; ++b) s += (double)partial[(long long)i * nblk + b];
     loss[i] = (float)s;
+}
+
+// ------------------------------------------------------------------------------------------------ bootstrapped cross-entropy
+// Hard-pixel mining: per image, loss = sum of the pixel losses l_i = -ce_term >= the keep-th largest of them (thresh); every pixel
+// tied with that value is kept (no tie-break: the kept count may exceed keep).  The forward stores l (4 B per pixel); an exact
+// radix select over its keys (radix_select.h: four 8-bit passes, block-local LDS histograms merged with integer atomics, one
+// histogram state per image) finds thresh; the sum pass and the backward kernels compare the stored l with it.
+
+// forward variant: l per pixel instead of the per-block sums (0 - x: an all-zero-weight pixel gives +0, never -0, so that the
+// comparison on floats and the order of the keys agree); grid (blocks_per_image, n), the pixel walk of mask_head_fwd_kernel
+__global__ void __launch_bounds__(256) mask_head_fwd_pixel_kernel(const float* __restrict__ logits, int h, int w, int fy, int fx,
+                                                                  const float* __restrict__ y_true, float4 cw, float* __restrict__ prob,
+                                                                  float* __restrict__ pixel_loss) {
+    const int ho = h * fy, wo = w * fx;
+    const long long npix = (long long)ho * wo;
+    const long long img = blockIdx.y;
+    const float ify = 1.f / (float)fy, ifx = 1.f / (float)fx;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+        const int ox = (int)(p % wo), oy = (int)(p / wo);
+        const float4 pr = softmax4(up_logits(logits, img, h, w, oy, ox, ify, ifx));
+        const long long off = (img * npix + p) * 4;
+        if (prob) st4(prob + off, pr);
+        pixel_loss[img * npix + p] = 0.f - ce_term(cw, ld4(y_true + off), pr);
+    }
+}
+
+// the same l from given probabilities (the standalone loss callable): y_true, p [total][4]
+__global__ void __launch_bounds__(256) pixel_ce_kernel(const float* __restrict__ y_true, const float* __restrict__ p, long long total, float4 cw,
+                                                       float* __restrict__ pixel_loss) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
+        pixel_loss[i] = 0.f - ce_term(cw, ld4(y_true + i * 4), ld4(p + i * 4));
+}
+
+// f(l) for every one of the npix losses of an image, block `blk` of `nblk`: 16-byte reads where the image's row is 16-byte aligned
+template <typename F>
+__device__ __forceinline__ void for_each_loss(const float* __restrict__ v, int npix, int blk, int nblk, F f) {
+    if ((npix & 3) == 0) {
+        const int n4 = npix >> 2;
+        for (int i = blk * 256 + (int)threadIdx.x; i < n4; i += nblk * 256) {
+            const float4 q = ld4(v + 4 * (long long)i);
+            f(q.x); f(q.y); f(q.z); f(q.w);
+        }
+    } else {
+        for (int i = blk * 256 + (int)threadIdx.x; i < npix; i += nblk * 256) f(v[i]);
+    }
+}
+
+// one 8-bit pass of the select, grid (blocks, n): hist [n][4][256], zeroed by the host
+__global__ void __launch_bounds__(256) bootstrap_hist_kernel(const float* __restrict__ pixel_loss, int npix, int keep, int* __restrict__ hist,
+                                                             int pass) {
+    __shared__ int lh[256];
+    __shared__ int bins[256];
+    __shared__ unsigned s_prefix;
+    __shared__ int s_krem;
+    const int t = threadIdx.x;
+    int* st = hist + (long long)blockIdx.y * 1024;
+    radix_select_prefix(reinterpret_cast<const int(*)[256]>(st), pass, keep, lh, &s_prefix, &s_krem);
+    const unsigned prefix = s_prefix;
+    const int shift = 24 - 8 * pass;
+    const unsigned himask = pass == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
+    bins[t] = 0;
+    __syncthreads();
+    for_each_loss(pixel_loss + (long long)blockIdx.y * npix, npix, blockIdx.x, gridDim.x, [&](float l) {
+        const unsigned key = order_key(l);
+        if ((key & himask) == prefix) atomicAdd(&bins[(key >> shift) & 255u], 1);
+    });
+    __syncthreads();
+    if (bins[t] != 0) atomicAdd(&st[pass * 256 + t], bins[t]);
+}
+
+// sum pass, grid (blocks, n): thresh[img] = the float of the selected key; per block the sum and the count of the kept losses
+__global__ void __launch_bounds__(256) bootstrap_sum_kernel(const float* __restrict__ pixel_loss, int npix, int keep, const int* __restrict__ hist,
+                                                            float* __restrict__ thresh, float* __restrict__ partial, int* __restrict__ pcount) {
+    __shared__ int lh[256];
+    __shared__ float red[1][256];
+    __shared__ int redc[1][256];
+    __shared__ unsigned s_prefix;
+    __shared__ int s_krem;
+    radix_select_prefix(reinterpret_cast<const int(*)[256]>(hist + (long long)blockIdx.y * 1024), 4, keep, lh, &s_prefix, &s_krem);
+    const float thr = order_key_value(s_prefix);
+    if (blockIdx.x == 0 && threadIdx.x == 0) thresh[blockIdx.y] = thr;
+    float sum = 0.f;
+    int cnt = 0;
+    for_each_loss(pixel_loss + (long long)blockIdx.y * npix, npix, blockIdx.x, gridDim.x, [&](float l) {
+        const bool kept = l >= thr;
+        sum += kept ? l : 0.f;
+        cnt += kept ? 1 : 0;
+    });
+    const float v[1] = {sum};
+    const int c[1] = {cnt};
+    block_sum256(v, red);
+    block_sum256(c, redc);
+    if (threadIdx.x == 0) {
+        partial[(long long)blockIdx.y * gridDim.x + blockIdx.x] = red[0][0];
+        pcount[(long long)blockIdx.y * gridDim.x + blockIdx.x] = redc[0][0];
+    }
+}
+
+__global__ void bootstrap_final_kernel(const float* __restrict__ partial, const int* __restrict__ pcount, int nblk, int n, float* __restrict__ loss,
+                                       int* __restrict__ kept) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    int c = 0;
+    for (int b = 0; b < nblk; ++b) {
+        s += (double)partial[(long long)i * nblk + b];
+        c += pcount[(long long)i * nblk + b];
+    }
+    if (loss != nullptr) loss[i] = (float)s;
+    if (kept != nullptr) kept[i] = c;
 }
 
 // dice / dice_square forward: probabilities (optional) and per-block partial sums (I_c, T_c); grid (blocks_per_image, n),
@@ -145,7 +267,8 @@ __global__ void mask_dice_final_kernel(const float* __restrict__ partial, int nb
 // dlogits(low res) = sum over the full-res pixels that interpolate from it of weight * dz, dz = softmax'(dL/dp)
 __global__ void __launch_bounds__(256) mask_head_bwd_kernel(const float* __restrict__ logits, int n, int h, int w, int fy, int fx,
                                                             const float* __restrict__ y_true, float4 cw, float loss_scale,
-                                                            float* __restrict__ dlogits, int mode, const float* __restrict__ coef) {
+                                                            float* __restrict__ dlogits, int mode, const float* __restrict__ coef,
+                                                            const float* __restrict__ pixel_loss, const float* __restrict__ thresh) {
     const int ho = h * fy, wo = w * fx;
     const long long total = (long long)n * h * w;
     const float ify = 1.f / (float)fy, ifx = 1.f / (float)fx;
@@ -155,14 +278,18 @@ __global__ void __launch_bounds__(256) mask_head_bwd_kernel(const float* __restr
         const long long img = i / ((long long)w * h);
         const LerpWindow win = lerp_window(iy, ix, h, w, fy, fx);
         float4 acc = f4(0.f);
-        const float4 cA = mode != 0 ? ld4(coef + img * 8) : f4(0.f), cB = mode != 0 ? ld4(coef + img * 8 + 4) : f4(0.f);
+        const bool dice = mode == 1 || mode == 2;
+        const float4 cA = dice ? ld4(coef + img * 8) : f4(0.f), cB = dice ? ld4(coef + img * 8 + 4) : f4(0.f);
+        const float thr = mode == MASK_BOOTSTRAP ? thresh[img] : 0.f;
         for (int oy = win.oy0; oy <= win.oy1; ++oy) {
             const float wy = lerp_weight(oy, iy, h, ify);
             if (wy == 0.f) continue;
             for (int ox = win.ox0; ox <= win.ox1; ++ox) {
                 const float wx = lerp_weight(ox, ix, w, ifx);
                 if (wx == 0.f) continue;
-                axpy4(acc, wy * wx * loss_scale, mask_dz(logits, img, h, w, oy, ox, ify, ifx, y_true + ((img * ho + oy) * wo + ox) * 4, mode, cw, cA, cB));
+                const long long pix = (img * ho + oy) * wo + ox;
+                axpy4(acc, wy * wx * loss_scale,
+                      mask_dz(logits, img, h, w, oy, ox, ify, ifx, y_true + pix * 4, mode, cw, cA, cB, pixel_loss ? pixel_loss + pix : nullptr, thr));
             }
         }
         st4(dlogits + i * 4, acc);
@@ -182,7 +309,7 @@ struct MaskTile {
 };
 template <int F, int TL, int NT>
 __device__ __forceinline__ MaskTile mask_dz_fill(float4* dz, const float* logits, int h, int w, const float* y_true, float4 cw, int mode,
-                                                 const float* coef) {
+                                                 const float* coef, const float* pixel_loss, const float* thresh) {
     constexpr int R = TL * F + F;
     const int ho = h * F, wo = w * F;
     const float inv = 1.f / (float)F;
@@ -194,13 +321,17 @@ __device__ __forceinline__ MaskTile mask_dz_fill(float4* dz, const float* logits
     t.img = b / tiles_y;
     t.iy0 = ty * TL; t.ix0 = tx * TL;
     t.oyb = t.iy0 * F - F / 2; t.oxb = t.ix0 * F - F / 2;
-    const float4 cA = mode != 0 ? ld4(coef + t.img * 8) : f4(0.f), cB = mode != 0 ? ld4(coef + t.img * 8 + 4) : f4(0.f);
+    const bool dice = mode == 1 || mode == 2;
+    const float4 cA = dice ? ld4(coef + t.img * 8) : f4(0.f), cB = dice ? ld4(coef + t.img * 8 + 4) : f4(0.f);
+    const float thr = mode == MASK_BOOTSTRAP ? thresh[t.img] : 0.f;
     for (int i = threadIdx.x; i < R * R; i += NT) {
         const int ry = i / R, rx = i - ry * R;
         const int oy = t.oyb + ry, ox = t.oxb + rx;
         float4 v = f4(0.f);
-        if (oy >= 0 && oy < ho && ox >= 0 && ox < wo)
-            v = mask_dz(logits, t.img, h, w, oy, ox, inv, inv, y_true + ((t.img * ho + oy) * wo + ox) * 4, mode, cw, cA, cB);
+        if (oy >= 0 && oy < ho && ox >= 0 && ox < wo) {
+            const long long pix = (t.img * ho + oy) * wo + ox;
+            v = mask_dz(logits, t.img, h, w, oy, ox, inv, inv, y_true + pix * 4, mode, cw, cA, cB, pixel_loss ? pixel_loss + pix : nullptr, thr);
+        }
         dz[i] = v;
     }
     __syncthreads();
@@ -212,10 +343,11 @@ __device__ __forceinline__ MaskTile mask_dz_fill(float4* dz, const float* logits
 template <int F, int TL>
 __global__ void __launch_bounds__(TL * TL) mask_head_bwd_tile_kernel(const float* __restrict__ logits, int n, int h, int w,
                                                                        const float* __restrict__ y_true, float4 cw, float loss_scale,
-                                                                       float* __restrict__ dlogits, int mode, const float* __restrict__ coef) {
+                                                                       float* __restrict__ dlogits, int mode, const float* __restrict__ coef,
+                                                                       const float* __restrict__ pixel_loss, const float* __restrict__ thresh) {
     constexpr int R = TL * F + F;
     extern __shared__ float4 dz[];                    // [R][R]
-    const MaskTile tile = mask_dz_fill<F, TL, TL * TL>(dz, logits, h, w, y_true, cw, mode, coef);
+    const MaskTile tile = mask_dz_fill<F, TL, TL * TL>(dz, logits, h, w, y_true, cw, mode, coef, pixel_loss, thresh);
     const float inv = 1.f / (float)F;
     const int ly = threadIdx.x / TL, lx = threadIdx.x - ly * TL;
     const int iy = tile.iy0 + ly, ix = tile.ix0 + lx;
@@ -248,11 +380,13 @@ __global__ void __launch_bounds__(TL * TL) mask_head_bwd_tile_kernel(const float
 template <int F, int TL, int PARTS>
 __global__ void __launch_bounds__(TL * TL * PARTS) mask_head_bwd_tile_split_kernel(const float* __restrict__ logits, int n, int h, int w,
                                                                                      const float* __restrict__ y_true, float4 cw, float loss_scale,
-                                                                                     float* __restrict__ dlogits, int mode, const float* __restrict__ coef) {
+                                                                                     float* __restrict__ dlogits, int mode, const float* __restrict__ coef,
+                                                                                     const float* __restrict__ pixel_loss,
+                                                                                     const float* __restrict__ thresh) {
     constexpr int R = TL * F + F;
     extern __shared__ float4 dz[];                    // [R][R] + [PARTS][TL * TL]
     float4* red = dz + R * R;
-    const MaskTile tile = mask_dz_fill<F, TL, TL * TL * PARTS>(dz, logits, h, w, y_true, cw, mode, coef);
+    const MaskTile tile = mask_dz_fill<F, TL, TL * TL * PARTS>(dz, logits, h, w, y_true, cw, mode, coef, pixel_loss, thresh);
     const float inv = 1.f / (float)F;
     const int pix = threadIdx.x % (TL * TL), part = threadIdx.x / (TL * TL);
     const int ly = pix / TL, lx = pix - ly * TL;
@@ -341,33 +475,64 @@ int launch_with_lds(ssdseg_ctx* ctx, const char* name, double bytes, long long b
     return 0;
 }
 
-// mode 0: cross-entropy (cwh: the class weights); 1 / 2: dice / dice_square (coef: mask_dice_final_kernel's)
+// mode 0: cross-entropy (cwh: the class weights); 1 / 2: dice / dice_square (coef: mask_dice_final_kernel's); MASK_BOOTSTRAP:
+// bootstrapped cross-entropy (cwh, and the forward's pixel_loss [n][H*W] and thresh [n]; both NULL in every other mode)
 int mask_head_bwd_launch(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int fy, int fx, const float* y_true, const float* cwh,
-                         float loss_scale, float* dlogits, int mode, const float* coef) {
-    const double bytes = 16.0 * n * h * fy * wdt * fx;
+                         float loss_scale, float* dlogits, int mode, const float* coef, const float* pixel_loss = nullptr,
+                         const float* thresh = nullptr) {
+    const double bytes = (pixel_loss ? 20.0 : 16.0) * n * h * fy * wdt * fx;
     const float4 cw = f4_of(cwh);
     const bool tiles = env_pick("SSDSEG_MASK_BWD", {"gather"}) == 0;      // "gather": the one-thread-per-pixel kernel (A/B runs, parity tests)
     if (tiles && fy == 4 && fx == 4) {
         constexpr int F = 4, TL = 16, R = TL * F + F;
         return launch_with_lds<mask_head_bwd_tile_kernel<F, TL>>(ctx, "(mask_head_bwd_tile_kernel<F, TL>)", bytes, (long long)n * cdiv(h, TL) * cdiv(wdt, TL),
-                                                                  TL * TL, R * R * sizeof(float4), logits, n, h, wdt, y_true, cw, loss_scale, dlogits, mode, coef);
+                                                                  TL * TL, R * R * sizeof(float4), logits, n, h, wdt, y_true, cw, loss_scale, dlogits, mode, coef,
+                                                                  pixel_loss, thresh);
     }
     if (tiles && fy == 8 && fx == 8) {
         constexpr int F = 8, TL = 8, PARTS = 4, R = TL * F + F;
         return launch_with_lds<mask_head_bwd_tile_split_kernel<F, TL, PARTS>>(ctx, "(mask_head_bwd_tile_split_kernel<F, TL, PARTS>)", bytes,
                                                                                (long long)n * cdiv(h, TL) * cdiv(wdt, TL), TL * TL * PARTS,
                                                                                (size_t)(R * R + PARTS * TL * TL) * sizeof(float4), logits, n, h, wdt, y_true, cw,
-                                                                               loss_scale, dlogits, mode, coef);
+                                                                               loss_scale, dlogits, mode, coef, pixel_loss, thresh);
     }
     SSDSEG_LAUNCH(ctx, bytes, 0.0, mask_head_bwd_kernel, dim3(ew_blocks((long long)n * h * wdt)), dim3(256), 0, logits, n, h, wdt, fy, fx, y_true, cw,
-                  loss_scale, dlogits, mode, coef);
+                  loss_scale, dlogits, mode, coef, pixel_loss, thresh);
     SSDSEG_LAUNCH_CHECK();
+    return 0;
+}
+
+// The select and the sum over pixel_loss [n][npix]: thresh [n], and loss / kept [n] where asked for.  Workspace (behind `front`
+// bytes the caller keeps): hist [n][4][256] | partial [n][nblk] | pcount [n][nblk].
+int bootstrap_blocks(int npix) {
+    const int nblk = cdiv(npix, 256 * 16);
+    return nblk > 32 ? 32 : nblk;
+}
+size_t bootstrap_ws_bytes(int n, int npix) { return (size_t)n * (4096 + 8 * (size_t)bootstrap_blocks(npix)); }
+int bootstrap_select_launch(ssdseg_ctx* ctx, const float* pixel_loss, int n, int npix, int keep, void* ws, float* thresh, int* kept, float* loss) {
+    const int nblk = bootstrap_blocks(npix);
+    int* hist = (int*)ws;
+    float* partial = (float*)((char*)ws + (size_t)n * 4096);
+    int* pcount = (int*)(partial + (size_t)n * nblk);
+    SSDSEG_HIP(hipMemsetAsync(hist, 0, (size_t)n * 4096, ctx->stream));
+    for (int pass = 0; pass < 4; ++pass) {
+        SSDSEG_LAUNCH(ctx, 4.0 * n * npix, 0.0, bootstrap_hist_kernel, dim3(nblk, n), dim3(256), 0, pixel_loss, npix, keep, hist, pass);
+        SSDSEG_LAUNCH_CHECK();
+    }
+    SSDSEG_LAUNCH(ctx, 4.0 * n * npix, 0.0, bootstrap_sum_kernel, dim3(nblk, n), dim3(256), 0, pixel_loss, npix, keep, (const int*)hist, thresh, partial,
+                  pcount);
+    SSDSEG_LAUNCH_CHECK();
+    if (loss != nullptr || kept != nullptr) {
+        SSDSEG_LAUNCH(ctx, 8.0 * n * nblk, 0.0, bootstrap_final_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (const float*)partial, (const int*)pcount, nblk,
+                      n, loss, kept);
+        SSDSEG_LAUNCH_CHECK();
+    }
     return 0;
 }
 
 }  // namespace
 
-// what the four mask-head entry points check first (a macro: SSDSEG_ARG reports under, and returns from, the entry point's own name)
+// what the mask-head entry points check first (a macro: SSDSEG_ARG reports under, and returns from, the entry point's own name)
 #define MASK_HEAD_ARGS()                                                                                       \
     SSDSEG_ARG(ctx != nullptr, 1);                                                                             \
     SSDSEG_ARG(logits != nullptr, 2);                                                                          \
@@ -438,6 +603,62 @@ int ssdseg_mask_head_bwd(ssdseg_ctx* ctx, const float* logits, int n, int h, int
     SSDSEG_ARG(class_weights_host != nullptr, 10);
     SSDSEG_ARG(dlogits != nullptr, 12);
     return mask_head_bwd_launch(ctx, logits, n, h, wdt, fy, fx, y_true, class_weights_host, loss_scale, dlogits, 0, nullptr);
+}
+
+int ssdseg_mask_head_fwd_bootstrap(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx, const float* y_true,
+                                   const float* class_weights_host, int keep, float* prob, float* pixel_loss, float* thresh, int* kept,
+                                   float* loss) {
+    MASK_HEAD_ARGS();
+    SSDSEG_ARG(y_true != nullptr, 9);
+    SSDSEG_ARG(class_weights_host != nullptr, 10);
+    const long long npix = (long long)h * fy * wdt * fx;
+    SSDSEG_ARG(npix <= 0x7FFFFFFFLL, 4);
+    SSDSEG_ARG(keep >= 1 && keep <= npix, 11);
+    SSDSEG_ARG(pixel_loss != nullptr, 13);
+    SSDSEG_ARG(thresh != nullptr, 14);
+    void* ws;
+    int rc = ssdseg_workspace(ctx, bootstrap_ws_bytes(n, (int)npix), &ws);
+    if (rc) return rc;
+    SSDSEG_LAUNCH(ctx, n * npix * (20.0 + (prob ? 16.0 : 0.0)), 0.0, mask_head_fwd_pixel_kernel, dim3(partial_blocks(npix, 256), n), dim3(256), 0, logits,
+                  h, wdt, fy, fx, y_true, f4_of(class_weights_host), prob, pixel_loss);
+    SSDSEG_LAUNCH_CHECK();
+    return bootstrap_select_launch(ctx, pixel_loss, n, (int)npix, keep, ws, thresh, kept, loss);
+}
+
+int ssdseg_mask_head_bwd_bootstrap(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx, const float* y_true,
+                                   const float* class_weights_host, const float* pixel_loss, const float* thresh, float loss_scale,
+                                   float* dlogits) {
+    MASK_HEAD_ARGS();
+    SSDSEG_ARG(y_true != nullptr, 9);
+    SSDSEG_ARG(class_weights_host != nullptr, 10);
+    SSDSEG_ARG(pixel_loss != nullptr, 11);
+    SSDSEG_ARG(thresh != nullptr, 12);
+    SSDSEG_ARG(dlogits != nullptr, 14);
+    return mask_head_bwd_launch(ctx, logits, n, h, wdt, fy, fx, y_true, class_weights_host, loss_scale, dlogits, MASK_BOOTSTRAP, nullptr, pixel_loss,
+                                thresh);
+}
+
+int ssdseg_bootstrap_ce_loss(ssdseg_ctx* ctx, const float* y_true, const float* p, int n, int hw, int c, const float* class_weights_host,
+                             int keep, float* loss) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    SSDSEG_ARG(y_true != nullptr, 2);
+    SSDSEG_ARG(p != nullptr, 3);
+    SSDSEG_ARG(n > 0 && hw > 0, 4);
+    SSDSEG_ARG(c == 4, 6);
+    SSDSEG_ARG(class_weights_host != nullptr, 7);
+    SSDSEG_ARG(keep >= 1 && keep <= hw, 8);
+    SSDSEG_ARG(loss != nullptr, 9);
+    // workspace: pixel_loss [n][hw] | thresh [n] (both rounded up to 16 bytes) | the select's
+    const size_t pl_bytes = ((size_t)n * hw * 4 + 15) & ~(size_t)15, th_bytes = ((size_t)n * 4 + 15) & ~(size_t)15;
+    void* ws;
+    int rc = ssdseg_workspace(ctx, pl_bytes + th_bytes + bootstrap_ws_bytes(n, hw), &ws);
+    if (rc) return rc;
+    float* pixel_loss = (float*)ws;
+    float* thresh = (float*)((char*)ws + pl_bytes);
+    const long long total = (long long)n * hw;
+    SSDSEG_LAUNCH(ctx, 36.0 * total, 0.0, pixel_ce_kernel, dim3(ew_blocks(total)), dim3(256), 0, y_true, p, total, f4_of(class_weights_host), pixel_loss);
+    SSDSEG_LAUNCH_CHECK();
+    return bootstrap_select_launch(ctx, pixel_loss, n, hw, keep, (char*)ws + pl_bytes + th_bytes, thresh, nullptr, loss);
 }
 
 int ssdseg_metric_mask_iou(ssdseg_ctx* ctx, const float* src, int n, int h, int wdt, int c, int fy, int fx, int from_logits,

@@ -579,12 +579,22 @@ class MaskHeadOp(Op):
         self.class_weights: Optional[H.DeviceBuffer] = None
         self.loss: Optional[H.DeviceBuffer] = None
         self.loss_scale = 0.0
-        self.kind = "cross_entropy"                       # | "dice" | "dice_square" (reference losses.py:175-307)
+        self.kind = "cross_entropy"                       # | "dice" | "dice_square" (reference losses.py:175-307) | "bootstrapped_cross_entropy"
         self.coef: Optional[H.DeviceBuffer] = None        # dice: per-image backward coefficients left by the forward
+        # bootstrapped cross-entropy: pixels kept per image, and what the forward leaves for the backward -- every pixel's loss
+        # [n][H*W], the per-image threshold [n] -- and the per-image kept count [n]
+        self.keep = 0
+        self.pixel_loss: Optional[H.DeviceBuffer] = None
+        self.thresh: Optional[H.DeviceBuffer] = None
+        self.kept: Optional[H.DeviceBuffer] = None
 
     def fwd(self):
         s = self.logits.store
         prob = self.prob.buf if self.prob is not None else None
+        if self.loss is not None and self.kind == "bootstrapped_cross_entropy":
+            self.e.ctx.call("ssdseg_mask_head_fwd_bootstrap", s.buf, s.n, s.h, s.w, s.c, self.fy, self.fx, self.y_true, self.class_weights,
+                            self.keep, prob, self.pixel_loss, self.thresh, self.kept, self.loss)
+            return
         if self.loss is not None and self.kind != "cross_entropy":
             self.e.ctx.call("ssdseg_mask_head_fwd_dice", s.buf, s.n, s.h, s.w, s.c, self.fy, self.fx, self.y_true, self.class_weights,
                             1 if self.kind == "dice_square" else 0, prob, self.loss, self.coef)
@@ -598,6 +608,10 @@ class MaskHeadOp(Op):
         s = self.logits.store
         g, acc = s.grad_slot()
         assert acc == 0
+        if self.kind == "bootstrapped_cross_entropy":
+            self.e.ctx.call("ssdseg_mask_head_bwd_bootstrap", s.buf, s.n, s.h, s.w, s.c, self.fy, self.fx, self.y_true, self.class_weights,
+                            self.pixel_loss, self.thresh, self.loss_scale, g)
+            return
         if self.kind != "cross_entropy":
             self.e.ctx.call("ssdseg_mask_head_bwd_dice", s.buf, s.n, s.h, s.w, s.c, self.fy, self.fx, self.y_true, self.coef,
                             1 if self.kind == "dice_square" else 0, self.loss_scale, g)
@@ -1456,13 +1470,20 @@ class Engine:
             w = float(loss_weights.get(name, 1.0))
             v = self.vals[id(t)]
             if "mask_head" in v.meta:
-                if getattr(fn, "loss_kind", None) not in ("cross_entropy", "dice", "dice_square"):
+                if getattr(fn, "loss_kind", None) not in ("cross_entropy", "dice", "dice_square", "bootstrapped_cross_entropy"):
                     raise NotImplementedError(f"loss for output {name}: the mask head trains with ssdseglib.losses.cross_entropy / dice / "
-                                              "dice_square")
+                                              "dice_square / bootstrapped_cross_entropy")
                 op: MaskHeadOp = v.meta["mask_head"]
                 op.kind = fn.loss_kind
-                op.coef = self.ctx.empty((b, 8)) if op.kind != "cross_entropy" else None
+                op.coef = self.ctx.empty((b, 8)) if op.kind in ("dice", "dice_square") else None
                 s = op.logits.store
+                op.keep, op.pixel_loss, op.thresh, op.kept = 0, None, None, None
+                if op.kind == "bootstrapped_cross_entropy":
+                    pixels = s.h * op.fy * s.w * op.fx
+                    op.keep = LS.bootstrap_keep(fn.keep_fraction, pixels)
+                    op.pixel_loss = self.ctx.empty((b, pixels))
+                    op.thresh = self.ctx.empty(b)
+                    op.kept = self.ctx.empty(b, np.int32)
                 op.y_true = self.ctx.empty((b, s.h * op.fy, s.w * op.fx, s.c))
                 op.class_weights = (C.c_float * 4)(*[float(x) for x in fn.classes_weights])
                 op.loss = self.ctx.empty(b)

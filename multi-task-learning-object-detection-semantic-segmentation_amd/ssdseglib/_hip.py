@@ -120,6 +120,9 @@ _SIGNATURES = {
     "ssdseg_mask_head_bwd": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_f), _f, _vp],
     "ssdseg_mask_head_fwd_dice": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_f), _i, _vp, _vp, _vp],
     "ssdseg_mask_head_bwd_dice": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _f, _vp],
+    "ssdseg_mask_head_fwd_bootstrap": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_f), _i, _vp, _vp, _vp, _vp, _vp],
+    "ssdseg_mask_head_bwd_bootstrap": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_f), _vp, _vp, _f, _vp],
+    "ssdseg_bootstrap_ce_loss": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), _i, _vp],
     "ssdseg_head_gather": [_vp, _VP, _vp, _i, _i, _i, _i, _i, _i],
     "ssdseg_softmax_rows": [_vp, _VP, _vp, _i, _i],
     "ssdseg_det_loss": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],

@@ -4,6 +4,7 @@ passed to `model.compile(loss={...})` they select the fused loss ops of the engi
 where the gradient comes out of the same launch.
 """
 import ctypes as C
+import math
 from typing import Callable, List
 
 import numpy as np
@@ -92,6 +93,49 @@ def _mask_loss(mode: int, name: str, kind: str, classes_weights: List[float]) ->
     loss_fn.__name__ = name
     loss_fn.classes_weights = weights
     loss_fn.loss_kind = kind
+    return loss_fn
+
+
+def bootstrap_keep(keep_fraction: float, pixels: int) -> int:
+    """pixels kept per image by `bootstrapped_cross_entropy`: ceil(keep_fraction * pixels) in double, at least 1, at most all"""
+    return min(int(pixels), max(1, math.ceil(float(keep_fraction) * int(pixels))))
+
+
+def bootstrapped_cross_entropy(classes_weights: List[float], keep_fraction: float = 0.25) -> Callable:
+    """weighted pixel cross-entropy over the hardest pixels of each image only (hard-pixel mining, DeepLab's bootstrapped
+    cross-entropy; not in the reference): with l_i = -sum_c w_c y_ic log(clip p_ic) the `cross_entropy` term of pixel i and
+    keep = min(H W, max(1, ceil(keep_fraction H W))), an image's loss is the sum of the l_i >= its keep-th largest l.  Every pixel
+    tied with the keep-th value is kept (no tie-break by index), so more than `keep` pixels may count.  The selection is per
+    image: no image depends on the rest of its batch.  keep_fraction = 1 is `cross_entropy`."""
+    try:
+        weights = tuple(float(w) for w in classes_weights)
+    except TypeError:
+        raise ValueError("classes_weights must hold one weight per class (4)") from None
+    if len(weights) != 4:
+        raise ValueError(f"classes_weights must hold one weight per class (4), got {len(weights)}")
+    if not all(np.isfinite(w) and w >= 0.0 for w in weights):
+        raise ValueError(f"classes_weights must be finite and >= 0, got {weights}")
+    try:
+        keep_fraction = float(keep_fraction)
+    except TypeError:
+        raise ValueError("keep_fraction must be a number in (0, 1]") from None
+    if not (np.isfinite(keep_fraction) and 0.0 < keep_fraction <= 1.0):
+        raise ValueError(f"keep_fraction must be finite and in (0, 1], got {keep_fraction}")
+
+    def loss_fn(y_true, y_pred):
+        y_true, y_pred = _f32(y_true), _f32(y_pred)
+        n, c = y_true.shape[0], y_true.shape[-1]
+        hw = int(np.prod(y_true.shape[1:-1]))
+        ctx = _ctx()
+        out = ctx.empty(n)
+        ctx.call("ssdseg_bootstrap_ce_loss", ctx.array(y_true), ctx.array(y_pred), n, hw, c, (C.c_float * 4)(*weights), bootstrap_keep(keep_fraction, hw),
+                 out)
+        return out.download()
+
+    loss_fn.__name__ = "bootstrapped_cross_entropy_loss"
+    loss_fn.classes_weights = weights
+    loss_fn.keep_fraction = keep_fraction
+    loss_fn.loss_kind = "bootstrapped_cross_entropy"
     return loss_fn
 
 
