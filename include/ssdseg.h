@@ -288,6 +288,8 @@ int ssdseg_gview_materialize(ssdseg_ctx* ctx, const ssdseg_gview* dy, int ld, in
  * finalize: partial (sum, sumsq)[nparts][2][c] over `count` samples per channel ->
  *   mean, biased var -> scale = gamma*rsqrt(var+eps), shift = beta - mean*scale, invstd;
  *   moving_mean <- mom*mm + (1-mom)*mean; moving_var <- mom*mv + (1-mom)*var*count/(count-1) (Bessel, App. B.3).
+ *   The fold is float64; var is clamped at 0 (float32 partial sums of a constant channel can fold to slightly less), and
+ *   count == 1 (the GAP branch at batch 1) feeds the biased var to moving_var: no 0/0 factor.  moving_* may be NULL in training.
  * training == 0: scale/shift from the moving statistics (inference), partials ignored. */
 int ssdseg_bn_finalize(ssdseg_ctx* ctx, const float* stats, int nparts, int c, double count, const float* gamma,
                        const float* beta, float eps, float momentum, float* moving_mean, float* moving_var,
