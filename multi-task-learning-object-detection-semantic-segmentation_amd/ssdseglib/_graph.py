@@ -409,20 +409,20 @@ class Model:
         self._compiled = dict(optimizer=optimizer, loss=loss or {}, loss_weights=loss_weights or {}, metrics=metrics or {})
 
     def __call__(self, x, training=False):
-        from . import _engine
-        return _engine.run_forward(self, x, training)
+        from . import _fit
+        return _fit.run_forward(self, x, training)
 
     def predict(self, data, verbose=0):
-        from . import _engine
-        return _engine.run_predict(self, data)
+        from . import _fit
+        return _fit.run_predict(self, data)
 
     def fit(self, data, epochs=1, validation_data=None, verbose=0):
-        from . import _engine
-        return _engine.run_fit(self, data, epochs, validation_data, verbose)
+        from . import _fit
+        return _fit.run_fit(self, data, epochs, validation_data, verbose)
 
     def train_on_batch(self, x, y=None):
-        from . import _engine
-        return _engine.run_train_on_batch(self, x, y)
+        from . import _fit
+        return _fit.run_train_on_batch(self, x, y)
 
     def save(self, path):
         """Own checkpoint: one .npz keyed `<layer>/<weight>` with Keras' names/shapes."""

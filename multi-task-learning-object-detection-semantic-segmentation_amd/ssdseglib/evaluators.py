@@ -181,9 +181,9 @@ def evaluate_on_device(model_inference, data, labels_codes: List[int], label_cod
     detections = {pair: [] for pair in pairs}
     iou_sum, seen = np.zeros(n_cls, np.float64), 0
 
-    from . import _engine
+    from . import _fit
     for batch in _plain_batches(data):
-        iou, per_pair = _engine.run_evaluate(model_inference, batch, pairs)
+        iou, per_pair = _fit.run_evaluate(model_inference, batch, pairs)
         for row in iou:
             iou_sum += row.astype(np.float64)
             seen += 1

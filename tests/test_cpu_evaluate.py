@@ -110,14 +110,14 @@ def _compact(flip=None, rgb_draws=None):
 @pytest.fixture()
 def no_device(monkeypatch):
     """any attempt to open a device context or to lower an engine fails the test"""
-    from ssdseglib import _engine, _hip
+    from ssdseglib import _engine, _fit, _hip
 
     def refuse(*a, **k):
         raise AssertionError("evaluate_on_device touched the device before rejecting its arguments")
 
     monkeypatch.setattr(_hip.Context, "__init__", refuse)
     monkeypatch.setattr(_engine, "engine_for", refuse)
-    monkeypatch.setattr(_engine, "run_evaluate", refuse)
+    monkeypatch.setattr(_fit, "run_evaluate", refuse)
 
 
 def test_rejects_suppress_background_boxes(no_device):

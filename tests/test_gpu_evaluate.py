@@ -88,7 +88,7 @@ def test_mask_jaccard_kernel_rejects_bad_arguments(ctx, guards):
 # ------------------------------------------------------------------------------------------------------ 2. the best-IoU kernel
 def test_det_best_iou_kernel(ctx, guards):
     from ssdseglib import evaluators
-    from ssdseglib._engine import _CompactLoader
+    from ssdseglib._loaders import _CompactLoader
     n, r, gmax = 4, 10, _CompactLoader.GMAX
     rng = np.random.default_rng(11)
     counts = np.array([0, 1, 3, gmax], np.int32)

@@ -108,13 +108,14 @@ def _device_encoded(cb, targets):
 
 def test_compact_batch_fills_the_step_buffers_like_the_oracle(ctx, guards, rng):
     """the engine's input / mask / label / offset buffers after a compact hand-over == the oracle's float tensors, bit for bit"""
-    from ssdseglib import _engine as E
+    from ssdseglib import _engine as E, _loaders as LD
     E.set_default_context(ctx)
     (cb, want_img, want), = _compact_batches(rng, (3,))
     _, _, model = build(seed=5)
     _compile(model)
     eng = E.engine_for(model, 3, True)
-    ld = E._compact_loader(eng, cb)
+    ld = LD.loader_for(eng, cb)
+    assert type(ld) is LD._CompactLoader
     ld.stage(cb)
     ld.consume()
     np.testing.assert_array_equal(eng.input_store.buf.download().reshape(want_img.shape), want_img)

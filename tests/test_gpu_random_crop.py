@@ -222,7 +222,9 @@ PICK = [4, 0, 2]
 
 
 def _filled(eng, loader, batch):
-    ld = loader(eng, batch)
+    from ssdseglib._loaders import loader_for
+    ld = loader_for(eng, batch)
+    assert type(ld) is loader
     ld.stage(batch)
     ld.consume()
     return _buffers(eng)
@@ -232,7 +234,7 @@ def test_cropped_batches_fill_the_step_buffers_alike(ctx, guards, rng):
     """a ResidentBatch with windows == its compact copy == a plain CompactBatch cropped on the host by the spec (same flips and
     draws, no windows): crop, then flip, then colour -- for every combination of flips and colour draws"""
     import ssdseglib
-    from ssdseglib import datacoder as D, _engine as E
+    from ssdseglib import datacoder as D, _engine as E, _loaders as LD
     E.set_default_context(ctx)
     ds, cb = _resident(rng, 5)
     _, _, model = build(seed=5)
@@ -249,9 +251,9 @@ def test_cropped_batches_fill_the_step_buffers_alike(ctx, guards, rng):
         assert img[1].tobytes() == cb.images[PICK[1]].tobytes() and np.array_equal(gts[1], cb.ground_truth[PICK[1]])      # the identity
         assert img[0].tobytes() != cb.images[PICK[0]].tobytes() and (idx[2] == FILL_CLASS).any()
         host = ssdseglib.datacoder.CompactBatch(img, idx, gts, compact.flip, cb.encoder, rgb_draws=draws)
-        got = _filled(eng, E._resident_loader, rb)
-        same = _filled(eng, E._compact_loader, compact)
-        want = _filled(eng, E._compact_loader, host)
+        got = _filled(eng, LD._ResidentLoader, rb)
+        same = _filled(eng, LD._CompactLoader, compact)
+        want = _filled(eng, LD._CompactLoader, host)
         assert want["__input__"].any()
         for name in want:
             assert got[name].tobytes() == want[name].tobytes(), ("resident", name, flip, draws)
@@ -259,14 +261,14 @@ def test_cropped_batches_fill_the_step_buffers_alike(ctx, guards, rng):
     # all-identity windows: the bytes of the batch without windows
     ident = np.tile(np.array([0, 0, W_, H_], np.float32), (3, 1))
     flip, draws = [0, 1, 1], _f32(HIGH)
-    plain = _filled(eng, E._resident_loader, ds.batch(PICK, flip, draws))
-    for loader, batch in ((E._resident_loader, ds.batch(PICK, flip, draws, crop_windows=ident, crop_fill=fill)),
-                          (E._compact_loader, ds.to_compact(ds.batch(PICK, flip, draws, crop_windows=ident)))):
+    plain = _filled(eng, LD._ResidentLoader, ds.batch(PICK, flip, draws))
+    for loader, batch in ((LD._ResidentLoader, ds.batch(PICK, flip, draws, crop_windows=ident, crop_fill=fill)),
+                          (LD._CompactLoader, ds.to_compact(ds.batch(PICK, flip, draws, crop_windows=ident)))):
         got = _filled(eng, loader, batch)
         for name in plain:
             assert got[name].tobytes() == plain[name].tobytes(), name
     # and a batch without windows after one with: the loader is back on its old path
-    again = _filled(eng, E._resident_loader, ds.batch(PICK, flip, draws))
+    again = _filled(eng, LD._ResidentLoader, ds.batch(PICK, flip, draws))
     assert all(again[name].tobytes() == plain[name].tobytes() for name in plain)
     # train_on_batch takes the same objects
     rb = ds.batch([3, 1, 4], [1, 0, 0], _f32(HIGH), crop_windows=WINDOWS, crop_fill=fill)
@@ -318,7 +320,7 @@ def test_fit_on_a_cropping_resident_dataset_equals_fit_on_its_compact_batches(ct
 
 def test_evaluate_on_device_refuses_a_cropped_batch(ctx, guards, rng):
     import ssdseglib
-    from ssdseglib import _engine as E
+    from ssdseglib import _engine as E, _fit
     E.set_default_context(ctx)
     ds, _ = _resident(rng, 3, flip=False)
     _, builder, model = build(seed=5)
@@ -330,4 +332,4 @@ def test_evaluate_on_device_refuses_a_cropped_batch(ctx, guards, rng):
         with pytest.raises(ValueError, match="crop windows"):
             ssdseglib.evaluators.evaluate_on_device(inference, data, [0, 1, 2, 3], 0, [0.5])
     with pytest.raises(ValueError, match="crop windows"):
-        E.run_evaluate(inference, rb, [(0.5, 0.5)])                  # the engine's own door is shut too
+        _fit.run_evaluate(inference, rb, [(0.5, 0.5)])                  # the engine's own door is shut too

@@ -212,7 +212,7 @@ def _buffers(eng):
 
 
 def test_resident_batch_fills_the_step_buffers_like_its_compact_copy(ctx, guards, rng):
-    from ssdseglib import _engine as E
+    from ssdseglib import _engine as E, _loaders as LD
     E.set_default_context(ctx)
     ds, cb = _resident(rng, 5)
     assert ds.num_samples == 5 and len(ds) == 2
@@ -225,11 +225,13 @@ def test_resident_batch_fills_the_step_buffers_like_its_compact_copy(ctx, guards
         assert compact.images.tobytes() == cb.images[ORDER[:3]].tobytes() and compact.mask_index.tobytes() == cb.mask_index[ORDER[:3]].tobytes()
         assert all(np.array_equal(g, cb.ground_truth[s]) for g, s in zip(compact.ground_truth, ORDER[:3]))
         assert compact.rgb_draws == rb.rgb_draws and compact.flip.tolist() == (flip or [0, 0, 0])
-        ld = E._resident_loader(eng, rb)
+        ld = LD.loader_for(eng, rb)
+        assert type(ld) is LD._ResidentLoader
         ld.stage(rb)
         ld.consume()
         got = _buffers(eng)
-        ld = E._compact_loader(eng, compact)
+        ld = LD.loader_for(eng, compact)
+        assert type(ld) is LD._CompactLoader
         ld.stage(compact)
         ld.consume()
         want = _buffers(eng)

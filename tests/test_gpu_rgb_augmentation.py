@@ -165,13 +165,14 @@ def _target_buffers(eng):
 
 @pytest.mark.gpu
 def test_loader_augments_only_the_image(ctx, guards, rng):
-    from ssdseglib import _engine as E
+    from ssdseglib import _engine as E, _loaders as LD
     E.set_default_context(ctx)
     (cb, _, _), = _compact_batches(rng, (3,))
     _, _, model = build(seed=5)
     _compile(model)
     eng = E.engine_for(model, 3, True)
-    ld = E._compact_loader(eng, cb)
+    ld = LD.loader_for(eng, cb)
+    assert type(ld) is LD._CompactLoader
     ld.stage(cb)
     ld.consume()
     plain = _target_buffers(eng)
