@@ -403,7 +403,7 @@ int ssdseg_det_loss_focal(ssdseg_ctx* ctx, const float* y_labels, const float* p
 /* exact top-k selection used by the mining step (tf.math.top_k semantics: larger value first, lower index
  * first among equals, losses.py:131): mask[i] = 1 for the k selected entries of values[n]. */
 int ssdseg_topk_mask(ssdseg_ctx* ctx, const float* values, int n, int k, uint8_t* mask);
-/* dice / dice_square (losses.py:175-264), API surface only: loss[n] from y_true, p [n][hw][c] */
+/* dice / dice_square (losses.py:175-264), API surface only: loss[n] from y_true, p [n][hw][c]; n <= 65535 */
 int ssdseg_dice_loss(ssdseg_ctx* ctx, const float* y_true, const float* p, int n, int hw, int c,
                      const float* class_weights_host, int squared, float* loss);
 
@@ -486,7 +486,7 @@ int ssdseg_crop_gt(ssdseg_ctx* ctx, const float* src_gt, const int32_t* src_cnt,
  * jaccard_iou_segmentation_masks_metric (metrics.py:35-47): SOFT Jaccard, inter = sum t*p, total = sum(t+p) over pixels,
  *   sum_c w_c * inter_c / (total_c - inter_c + 1e-7).  from_logits = 1: src = the low-resolution logits [n][h][w][4], p =
  *   softmax(bilinear x(fy,fx)) recomputed per pixel (the training step never stores output-mask); from_logits = 0:
- *   src = probabilities [n][h][w][4], fy = fx = 1.  y_true [n][h*fy][w*fx][4].  out [n]. */
+ *   src = probabilities [n][h][w][4], fy = fx = 1.  y_true [n][h*fy][w*fx][4].  out [n].  n <= 65535. */
 int ssdseg_metric_mask_iou(ssdseg_ctx* ctx, const float* src, int n, int h, int wdt, int c, int fy, int fx, int from_logits,
                            const float* y_true, const float* class_weights_host, float* out);
 /* categorical_accuracy_metric (metrics.py:204-216): per class #anchors with one_hot(argmax p)[c] == y_true[c], / a,
@@ -552,10 +552,11 @@ int ssdseg_channel_shuffle(ssdseg_ctx* ctx, const ssdseg_view* in, int ldi, floa
 int ssdseg_channel_gather(ssdseg_ctx* ctx, const ssdseg_view* in, int ldi, float* out, int ldo, long long m, int c_out,
                           const int32_t* table, int accumulate);
 /* rows x cols block copy between row-major matrices of different leading dimension: parameters between their exact Keras
- * shapes (flat bucket) and the zero-padded shapes of those units */
+ * shapes (flat bucket) and the zero-padded shapes of those units; rows * cols < 2^31 - 2^21 */
 int ssdseg_copy2d(ssdseg_ctx* ctx, float* dst, int ldd, const float* src, int lds, int rows, int cols);
 /* The same for a table of blocks in ONE launch.  `table` (device): ncopies rows of six 64-bit words {dst pointer, ldd, src pointer,
- * lds, rows, cols}; max_elems = the largest rows * cols of the table (sizes the grid), total_floats = their sum (timing registry).
+ * lds, rows, cols}; max_elems = the largest rows * cols of the table (sizes the grid; < 2^31 - 4096), total_floats = their sum
+ * (timing registry).
  * ShuffleNetV2 '1x' / '2x' (reference models.py:557-603: stage-2 branches of 58 / 122 channels) keep zero-padded copies of ~50
  * weight tensors: refreshing them and folding their gradients back was 160 launches of ~6 us per step. */
 int ssdseg_copy2d_batch(ssdseg_ctx* ctx, const long long* table, int ncopies, int max_elems, long long total_floats);

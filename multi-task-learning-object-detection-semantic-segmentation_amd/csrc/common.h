@@ -181,7 +181,8 @@ __device__ __forceinline__ void add4(float4& acc, float4 a) { acc.x += a.x; acc.
 
 // a = act(scale*x + shift) on a 4-channel vector; has_affine == false -> act(x)
 __device__ __forceinline__ float4 view_apply4(float4 x, float4 s, float4 t, bool has_affine, int act) {
-    // identity affine instead of a branch (fma(1, x, 0) == x exactly)
+    // identity affine instead of a branch: fma(1, x, 0) == x in value, but -0.f comes out as +0.f -- a kernel that only MOVES data
+    // (head_gather_kernel) must skip this for a plain view to keep the bits
     if (!has_affine) { s = make_float4(1.f, 1.f, 1.f, 1.f); t = make_float4(0.f, 0.f, 0.f, 0.f); }
     x.x = fmaf(s.x, x.x, t.x); x.y = fmaf(s.y, x.y, t.y); x.z = fmaf(s.z, x.z, t.z); x.w = fmaf(s.w, x.w, t.w);
     x.x = act_apply(x.x, act); x.y = act_apply(x.y, act); x.z = act_apply(x.z, act); x.w = act_apply(x.w, act);

@@ -21,7 +21,9 @@ __global__ void head_gather_kernel(const float* __restrict__ src, const float* _
             float4 s = f4(0.f), t = f4(0.f);
             const int c0 = r % c;
             if (aff) { s = ld4(scale + c0); t = ld4(shift + c0); }
-            st4(dst + strided, view_apply4(ld4(src + dense), s, t, aff, act));
+            float4 v = ld4(src + dense);
+            if (aff || act != SSDSEG_ACT_NONE) v = view_apply4(v, s, t, aff, act);   // a plain move keeps the bits: fma(1, -0.f, 0.f) is +0.f
+            st4(dst + strided, v);
         } else {
             st4(dst + dense, ld4(src + strided));
         }

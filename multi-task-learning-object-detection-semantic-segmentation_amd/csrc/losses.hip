@@ -523,7 +523,7 @@ int ssdseg_dice_loss(ssdseg_ctx* ctx, const float* y_true, const float* p, int n
     SSDSEG_ARG(ctx != nullptr, 1);
     SSDSEG_ARG(y_true != nullptr, 2);
     SSDSEG_ARG(p != nullptr, 3);
-    SSDSEG_ARG(n > 0 && hw > 0, 4);
+    SSDSEG_ARG(n > 0 && n <= 65535 && hw > 0, 4);   // the image is gridDim.y of dice_partial_kernel
     SSDSEG_ARG(c == 4, 6);
     SSDSEG_ARG(class_weights_host != nullptr, 7);
     SSDSEG_ARG(loss != nullptr, 9);

@@ -665,7 +665,7 @@ int ssdseg_metric_mask_iou(ssdseg_ctx* ctx, const float* src, int n, int h, int 
                            const float* y_true, const float* class_weights_host, float* out) {
     SSDSEG_ARG(ctx != nullptr, 1);
     SSDSEG_ARG(src != nullptr, 2);
-    SSDSEG_ARG(n > 0 && h > 0 && wdt > 0, 3);
+    SSDSEG_ARG(n > 0 && n <= 65535 && h > 0 && wdt > 0, 3);   // the image is gridDim.y of mask_iou_partial_kernel
     SSDSEG_ARG(c == 4, 6);
     SSDSEG_ARG(fy >= 1 && fx >= 1 && (from_logits || (fy == 1 && fx == 1)), 7);
     SSDSEG_ARG(y_true != nullptr, 10);

@@ -339,6 +339,8 @@ int ssdseg_copy2d(ssdseg_ctx* ctx, float* dst, int ldd, const float* src, int ld
     SSDSEG_ARG(dst != nullptr, 2);
     SSDSEG_ARG(src != nullptr, 4);
     SSDSEG_ARG(rows > 0 && cols > 0 && ldd >= cols && lds >= cols, 6);
+    // copy2d_kernel indexes the block's elements in int and steps by the whole grid: the last step must not pass 2^31 either
+    SSDSEG_ARG((long long)rows * cols < (1LL << 31) - 8192LL * 256, 6);
     SSDSEG_LAUNCH(ctx, 8.0 * rows * cols, 0.0, copy2d_kernel, dim3(ew_blocks((long long)rows * cols)), dim3(256), 0, dst, ldd, src, lds, rows, cols);
     SSDSEG_LAUNCH_CHECK();
     return 0;
@@ -348,7 +350,7 @@ int ssdseg_copy2d_batch(ssdseg_ctx* ctx, const long long* table, int ncopies, in
     SSDSEG_ARG(ctx != nullptr, 1);
     SSDSEG_ARG(table != nullptr, 2);
     SSDSEG_ARG(ncopies > 0, 3);
-    SSDSEG_ARG(max_elems > 0, 4);
+    SSDSEG_ARG(max_elems > 0 && max_elems < (1LL << 31) - 16LL * 256, 4);   // rows * cols of every row, in int plus one grid step
     const int gx = (max_elems + 255) / 256 < 16 ? (max_elems + 255) / 256 : 16;
     SSDSEG_LAUNCH(ctx, 8.0 * (double)total_floats, 0.0, copy2d_batch_kernel, dim3(gx, ncopies, 1), dim3(256), 0, table);
     SSDSEG_LAUNCH_CHECK();
