@@ -420,7 +420,9 @@ int ssdseg_encode_targets(ssdseg_ctx* ctx, const float* anchors_corners, int a, 
  * [b][h][w][3], uint8 class indices [b][h][w], ground-truth rows -- and these two calls (+ ssdseg_encode_targets) produce the
  * float32 image (tf.cast :327), the float32 one-hot mask [b][h][w][c] (tf.one_hot :332: an index >= c gives an all-zero row) and
  * the mirrored ground truth of the samples whose flip[n] != 0 (tf.image.flip_left_right :341-342; boxes xmin' = W - xmax,
- * xmax' = W - xmin :202-203, quirk Q8).  images_u8 or mask_index_u8 may be NULL (only the other is expanded); flip may be NULL. */
+ * xmax' = W - xmin :202-203, quirk Q8).  images_u8 or mask_index_u8 may be NULL (only the other is expanded); flip may be NULL.
+ * One image holds fewer than 2^31 bytes (h * w * 3 < 2^31, else the argument error for h): in-image offsets are 32-bit, as in
+ * ssdseg_rgb_augment, ssdseg_gather_inputs and ssdseg_crop_inputs; any b (launches of at most 65,535 samples). */
 int ssdseg_expand_inputs(ssdseg_ctx* ctx, const uint8_t* images_u8, const uint8_t* mask_index_u8, const uint8_t* flip, float* images_f32,
                          float* mask_onehot, int b, int h, int w, int c);
 /* gt [b][gmax][5] = (label, xmin, ymin, xmax, ymax), in place, rows g < gt_count[n] of the samples with flip[n] != 0 */

@@ -10,20 +10,18 @@
 // for operation in float32 (no FMA contraction -- this unit is built with -ffp-contract=off on top of the pragmas -- and the only
 // divisions, w / W and W / w, are done on the host, correctly rounded), so it agrees with it byte for byte
 // (tests/test_gpu_random_crop.py).  The source is a pool + a host index list, or a plain batch (index list NULL: n -> n); indices,
-// windows and fill travel BY VALUE in the kernel arguments, CROP_CHUNK samples per launch, as gather_sel does in inputs.hip.
+// windows and fill travel BY VALUE in the kernel arguments beside the gather_sel block of batch_sel.h, 64 samples per launch.
 #include <cmath>
 
-#include "common.h"
+#include "batch_sel.h"
 
 namespace {
 
-constexpr int CROP_CHUNK = 64;
 struct crop_sel {
-    int32_t index[CROP_CHUNK];       // source sample of output sample n0 + n
-    float win[CROP_CHUNK][4];        // (x0, y0, w, h)
-    float scale[CROP_CHUNK][2];      // crop_inputs: (sx, sy) = (w / W, h / H); crop_gt: (kx, ky) = (W / w, H / h)
-    uint32_t fill;                   // r | g << 8 | b << 16 | fill_class << 24
-    unsigned long long flip;         // bit n: the flip flag handed on to flip_out (the crop itself mirrors nothing)
+    gather_sel who;                          // the source sample; its flag is handed on to flip_out (the crop itself mirrors nothing)
+    float win[gather_sel::chunk][4];         // (x0, y0, w, h)
+    float scale[gather_sel::chunk][2];       // crop_inputs: (sx, sy) = (w / W, h / H); crop_gt: (kx, ky) = (W / w, H / h)
+    uint32_t fill;                           // r | g << 8 | b << 16 | fill_class << 24
 };
 
 // o + (i + 0.5) * s: the centre of output pixel i in source units
@@ -91,8 +89,8 @@ __global__ void __launch_bounds__(256) crop_inputs_kernel(const uint8_t* __restr
                                                           uint8_t* __restrict__ out_img, uint8_t* __restrict__ out_mask, uint8_t* __restrict__ flip_out,
                                                           int n0, int h, int w) {
     const int n = blockIdx.y, hw = h * w;
-    if (flip_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) flip_out[n0 + n] = (uint8_t)((sel.flip >> n) & 1ull);
-    const long long s = sel.index[n];
+    if (flip_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) flip_out[n0 + n] = (uint8_t)sel.who.mirrored(n0, n);
+    const long long s = sel.who.source(n0, n);
     const float wx0 = sel.win[n][0], wy0 = sel.win[n][1], sx = sel.scale[n][0], sy = sel.scale[n][1];
     const float fill[3] = {(float)(sel.fill & 0xffu), (float)((sel.fill >> 8) & 0xffu), (float)((sel.fill >> 16) & 0xffu)};
     const uint32_t fill_class = sel.fill >> 24;
@@ -141,7 +139,7 @@ __global__ void __launch_bounds__(64) crop_gt_kernel(const float* __restrict__ s
                                                      float* __restrict__ gt, int32_t* __restrict__ gt_count, int n0, int gmax, float width, float height) {
 #pragma clang fp contract(off)
     const int n = blockIdx.x, lane = threadIdx.x;
-    const long long s = sel.index[n];
+    const long long s = sel.who.source(n0, n);
     const float x0 = sel.win[n][0], y0 = sel.win[n][1], ww = sel.win[n][2], wh = sel.win[n][3], kx = sel.scale[n][0], ky = sel.scale[n][1];
     const bool identity = x0 == 0.f && y0 == 0.f && ww == width && wh == height;
     const float x1 = x0 + ww, y1 = y0 + wh;
@@ -191,25 +189,17 @@ bool windows_in_range(const float* win, int b, int h, int w) {
     return true;
 }
 
-bool indices_in_source(const int32_t* index_host, int b, int n_src) {
-    if (index_host == nullptr) return b <= n_src;              // n -> n
-    for (int i = 0; i < b; ++i)
-        if (index_host[i] < 0 || index_host[i] >= n_src) return false;
-    return true;
-}
-
 // samples [n0, n0 + count) of the host lists as one kernel-argument block; inverse: the scales of crop_gt
 crop_sel make_crop_sel(const int32_t* index_host, const float* win, int n0, int count, int h, int w, bool inverse, uint32_t fill,
                        const uint8_t* flip_host) {
     crop_sel sel;
     memset(&sel, 0, sizeof(sel));
+    sel.who = make_sel(index_host, flip_host, n0, count);
     for (int i = 0; i < count; ++i) {
         const float* q = win + 4 * (size_t)(n0 + i);
-        sel.index[i] = index_host != nullptr ? index_host[n0 + i] : n0 + i;
         for (int k = 0; k < 4; ++k) sel.win[i][k] = q[k];
         sel.scale[i][0] = inverse ? (float)w / q[2] : q[2] / (float)w;
         sel.scale[i][1] = inverse ? (float)h / q[3] : q[3] / (float)h;
-        if (flip_host != nullptr && flip_host[n0 + i] != 0) sel.flip |= 1ull << i;
     }
     sel.fill = fill;
     return sel;
@@ -241,19 +231,13 @@ int ssdseg_crop_inputs(ssdseg_ctx* ctx, const uint8_t* src_images, const uint8_t
     // dword stores: whole groups of 4 pixels per row and dword-aligned outputs (the taps are byte gathers: no condition on the source)
     const bool vec = w % 4 == 0 && (src_images == nullptr || ((uintptr_t)images_u8 & 3) == 0) && (src_masks == nullptr || ((uintptr_t)mask_index_u8 & 3) == 0);
     const int gx = vec ? cdiv(hw, 1024) : cdiv(hw, 256);
-    for (int n0 = 0; n0 < b; n0 += CROP_CHUNK) {
-        const int count = b - n0 < CROP_CHUNK ? b - n0 : CROP_CHUNK;
-        const crop_sel sel = make_crop_sel(index_host, windows_host, n0, count, h, w, false, fill, flip_host);
+    return for_each_chunk(b, gather_sel::chunk, [&](int n0, int count) {
         const double bytes = (double)count * hw * ((src_images ? 6.0 : 0.0) + (src_masks ? 2.0 : 0.0));
-        if (vec)
-            SSDSEG_LAUNCH(ctx, bytes, 0.0, crop_inputs_kernel<true>, dim3(gx, count), dim3(256), 0, src_images, src_masks, sel, images_u8, mask_index_u8,
-                          flip_host != nullptr ? flip_out : nullptr, n0, h, w);
-        else
-            SSDSEG_LAUNCH(ctx, bytes, 0.0, crop_inputs_kernel<false>, dim3(gx, count), dim3(256), 0, src_images, src_masks, sel, images_u8, mask_index_u8,
-                          flip_host != nullptr ? flip_out : nullptr, n0, h, w);
-        SSDSEG_LAUNCH_CHECK();
-    }
-    return 0;
+        return launch_vec<crop_inputs_kernel<true>, crop_inputs_kernel<false>>(
+            ctx, vec, "crop_inputs_kernel", bytes, dim3(gx, count), 256, src_images, src_masks,
+            make_crop_sel(index_host, windows_host, n0, count, h, w, false, fill, flip_host), images_u8, mask_index_u8,
+            flip_host != nullptr ? flip_out : nullptr, n0, h, w);
+    });
 }
 
 int ssdseg_crop_gt(ssdseg_ctx* ctx, const float* src_gt, const int32_t* src_cnt, int n_src, const int32_t* index_host, const float* windows_host,
@@ -269,14 +253,11 @@ int ssdseg_crop_gt(ssdseg_ctx* ctx, const float* src_gt, const int32_t* src_cnt,
     SSDSEG_ARG(h > 0 && w > 0 && h <= (1 << 24) && w <= (1 << 24), 11);
     SSDSEG_ARG(indices_in_source(index_host, b, n_src), 5);
     SSDSEG_ARG(windows_in_range(windows_host, b, h, w), 6);
-    for (int n0 = 0; n0 < b; n0 += CROP_CHUNK) {
-        const int count = b - n0 < CROP_CHUNK ? b - n0 : CROP_CHUNK;
-        const crop_sel sel = make_crop_sel(index_host, windows_host, n0, count, h, w, true, 0u, nullptr);
-        SSDSEG_LAUNCH(ctx, (40.0 * gmax + 8.0) * count, 0.0, crop_gt_kernel, dim3(count), dim3(64), 0, src_gt, src_cnt, sel, gt, gt_count, n0, gmax,
-                      (float)w, (float)h);
-        SSDSEG_LAUNCH_CHECK();
-    }
-    return 0;
+    return for_each_chunk(b, gather_sel::chunk, [&](int n0, int count) {
+        SSDSEG_LAUNCH(ctx, (40.0 * gmax + 8.0) * count, 0.0, crop_gt_kernel, dim3(count), dim3(64), 0, src_gt, src_cnt,
+                      make_crop_sel(index_host, windows_host, n0, count, h, w, true, 0u, nullptr), gt, gt_count, n0, gmax, (float)w, (float)h);
+        return launch_status("crop_gt_kernel");
+    });
 }
 
 }  // extern "C"

@@ -24,39 +24,24 @@
 //                          the bits of ssdseg_expand_inputs / ssdseg_rgb_augment on the same samples stacked on the host;
 //   ssdseg_gather_gt       its ground-truth rows and count, mirrored as ssdseg_flip_gt_boxes does, rows past the count zero
 // (tests/test_gpu_resident_dataset.py).
+// Each pass is ONE kernel -- expand_kernel, rgb_stats_kernel, rgb_apply_kernel -- templated on how a block learns its source
+// sample and its flip flag (batch_sel.h): plain_sel for the compact entry points, gather_sel for the indexed ones; and one host
+// function per pass (expand_pass, rgb_passes) that both kinds of entry point call.  In-image offsets are 32-bit (every entry
+// point refuses an image of 2^31 bytes or more), sample offsets 64-bit.
 #include <cmath>
 
-#include "common.h"
+#include "batch_sel.h"
 
 namespace {
 
-// one thread per OUTPUT pixel: 3 bytes + 1 byte in, 3 + c floats out (c <= 8; the one-hot row as float4 stores when c == 4)
-__global__ void __launch_bounds__(256) expand_inputs_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ midx, const uint8_t* __restrict__ flip,
-                                                            float* __restrict__ out_img, float* __restrict__ out_mask, int h, int w, int c,
-                                                            long long total) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int x = (int)(i % w);
-        const long long row = i / w;                 // (image, y)
-        const int n = (int)(row / h);
-        const bool f = flip != nullptr && flip[n] != 0;
-        const long long src = row * w + (f ? w - 1 - x : x);
-        if (img != nullptr) {
-            const uint8_t* p = img + src * 3;
-            float* o = out_img + i * 3;
-            o[0] = (float)p[0]; o[1] = (float)p[1]; o[2] = (float)p[2];
-        }
-        if (midx != nullptr) {
-            const int k = midx[src];
-            float* o = out_mask + i * c;
-            if (c == 4) {
-                st4(o, make_float4(k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f, k == 3 ? 1.f : 0.f));
-            } else {
-                for (int j = 0; j < c; ++j) o[j] = k == j ? 1.f : 0.f;
-            }
-        }
-    }
+// the x extent of a box mirrored left-right: xmin' = W - xmax, xmax' = W - xmin (quirk Q8)
+__device__ __forceinline__ void mirror_box(float width, float& xmin, float& xmax) {
+    const float lo = width - xmax;
+    xmax = width - xmin;
+    xmin = lo;
 }
 
+// in place: rows past the count and unflagged samples are left alone
 __global__ void flip_gt_boxes_kernel(float* __restrict__ gt, const int* __restrict__ count, const uint8_t* __restrict__ flip, int b, int gmax,
                                      float width) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;      // over b * gmax rows
@@ -64,9 +49,7 @@ __global__ void flip_gt_boxes_kernel(float* __restrict__ gt, const int* __restri
     const int n = i / gmax, g = i - n * gmax;
     if (flip[n] == 0 || g >= count[n]) return;
     float* r = gt + (long long)i * 5;                          // (label, xmin, ymin, xmax, ymax)
-    const float xmin = r[1], xmax = r[3];
-    r[1] = width - xmax;
-    r[3] = width - xmin;
+    mirror_box(width, r[1], r[3]);
 }
 
 // ---------------------------------------------------------------- colour augmentation (datacoder._augment_rgb)
@@ -131,7 +114,7 @@ __device__ __forceinline__ void load4px(const uint8_t* img, int p, float px[12])
 // pass 1: per block and channel, the sum of the hue- and saturation-adjusted values of its (up to) 1024 pixels of image
 // blockIdx.y, in a fixed order -> part[n][blockIdx.x][3].  Reads the pixels in storage order (the mean ignores the mirror).
 // VEC: every image row holds a multiple of 4 pixels.
-// (the body, shared with the gathering form below: `src` is the image, `part3` the block's 3 partial sums)
+// (the body: `src` is the image, `part3` the block's 3 partial sums)
 template <bool VEC>
 __device__ __forceinline__ void rgb_aug_stats_block(const uint8_t* __restrict__ src, float* __restrict__ part3, int hw, float hue, float sat) {
     const int p0 = blockIdx.x * AUG_BLOCK_PIX + threadIdx.x * AUG_PIX;
@@ -169,11 +152,11 @@ __device__ __forceinline__ void rgb_aug_stats_block(const uint8_t* __restrict__ 
     }
 }
 
-template <bool VEC>
-__global__ void __launch_bounds__(AUG_THREADS) rgb_aug_stats_kernel(const uint8_t* __restrict__ img, float* __restrict__ part, int hw,
-                                                                     float hue, float sat) {
+template <bool VEC, typename SEL>
+__global__ void __launch_bounds__(AUG_THREADS) rgb_stats_kernel(const uint8_t* __restrict__ src_img, SEL sel, float* __restrict__ part, int n0, int hw,
+                                                                 float hue, float sat) {
     const int n = blockIdx.y;
-    rgb_aug_stats_block<VEC>(img + (long long)n * hw * 3, part + ((long long)n * gridDim.x + blockIdx.x) * 3, hw, hue, sat);
+    rgb_aug_stats_block<VEC>(src_img + sel.source(n0, n) * hw * 3, part + ((long long)(n0 + n) * gridDim.x + blockIdx.x) * 3, hw, hue, sat);
 }
 
 // pass 2: means[n][c] = (sum of the nb block partials, in double, fixed order) / hw.  One wave per (channel, image).
@@ -188,7 +171,7 @@ __global__ void __launch_bounds__(64) rgb_aug_means_kernel(const float* __restri
 
 // pass 3: recompute the adjusted pixel from the uint8 input, contrast about the mean, brightness, clip; output pixel x of a
 // flagged image comes from source pixel w - 1 - x
-// (the body, shared with the gathering form below: `src` / `dst` are the image and its output, `mean3` its 3 means, `f` its flag)
+// (the body: `src` / `dst` are the image and its output, `mean3` its 3 means, `f` its flag)
 template <bool VEC>
 __device__ __forceinline__ void rgb_aug_apply_block(const uint8_t* __restrict__ src, float* __restrict__ dst, const float* __restrict__ mean3,
                                                     bool f, int h, int w, float hue, float sat, float con, float bri) {
@@ -230,146 +213,111 @@ __device__ __forceinline__ void rgb_aug_apply_block(const uint8_t* __restrict__ 
     }
 }
 
-template <bool VEC>
-__global__ void __launch_bounds__(AUG_THREADS) rgb_aug_apply_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ flip,
-                                                                     const float* __restrict__ means, float* __restrict__ out, int h, int w,
-                                                                     float hue, float sat, float con, float bri) {
+template <bool VEC, typename SEL>
+__global__ void __launch_bounds__(AUG_THREADS) rgb_apply_kernel(const uint8_t* __restrict__ src_img, SEL sel, const float* __restrict__ means,
+                                                                 float* __restrict__ out, int n0, int h, int w, float hue, float sat, float con,
+                                                                 float bri) {
     const int n = blockIdx.y;
-    const long long off = (long long)n * h * w * 3;
-    rgb_aug_apply_block<VEC>(img + off, out + off, means + n * 3, flip != nullptr && flip[n] != 0, h, w, hue, sat, con, bri);
+    const long long img = (long long)h * w * 3;
+    rgb_aug_apply_block<VEC>(src_img + sel.source(n0, n) * img, out + (n0 + n) * img, means + (n0 + n) * 3, sel.mirrored(n0, n), h, w, hue, sat, con,
+                             bri);
 }
 
-// ---------------------------------------------------------------- device-resident training set (datacoder.ResidentDataset)
-// The samples stay in HBM as the files hold them (pools of uint8 pixels, uint8 class indices, ground-truth rows); a batch is a
-// list of sample indices + flip flags drawn on the host each epoch (NB03#cell8: shuffle, read_and_encode, batch).  The list
-// travels BY VALUE in the kernel arguments, GATHER_CHUNK samples per launch: no host -> device copy of its own, nothing the
-// caller could overwrite while it is in flight, no synchronisation.  blockIdx.y is the sample within the chunk (wave-uniform
-// reads of the argument block); all pool offsets are 64-bit (index * h * w * 3 passes 2^32 at 4,661 samples of 480x640).
-constexpr int GATHER_CHUNK = 64;
-struct gather_sel {
-    int32_t index[GATHER_CHUNK];     // pool sample of output sample n0 + n
-    unsigned long long flip;         // bit n: mirror it
-};
-
-// ssdseg_expand_inputs' work on gathered samples.  VEC (w % 4 == 0, aligned buffers): four consecutive output pixels per thread
-// -- 3 dwords of pixels + 1 dword of class indices in, 3 + c float4 out; mirrored, they are the 4 source pixels ending at
-// w - 1 - x, reversed.  Otherwise one pixel per thread, as expand_inputs_kernel.
-template <bool VEC>
-__global__ void __launch_bounds__(256) gather_expand_kernel(const uint8_t* __restrict__ pool_img, const uint8_t* __restrict__ pool_midx,
-                                                            gather_sel sel, float* __restrict__ out_img, float* __restrict__ out_mask, int n0, int h,
-                                                            int w, int c) {
-    const int n = blockIdx.y, hw = h * w;
-    const long long s = sel.index[n];
-    const bool f = ((sel.flip >> n) & 1ull) != 0;
-    const long long o = (long long)(n0 + n) * hw;          // first output pixel of this sample
-    if (VEC) {
-        const int p0 = (blockIdx.x * 256 + threadIdx.x) * 4;
-        if (p0 >= hw) return;
-        const int y = p0 / w, x = p0 - y * w;
-        const int sp = y * w + (f ? w - 4 - x : x);
-        if (pool_img != nullptr) {
-            float px[12], q[12];
-            load4px(pool_img + s * hw * 3, sp, px);
-#pragma unroll
-            for (int j = 0; j < 12; ++j) q[j] = f ? px[3 * (3 - j / 3) + j % 3] : px[j];
-            float* d = out_img + (o + p0) * 3;
-            st4(d, make_float4(q[0], q[1], q[2], q[3]));
-            st4(d + 4, make_float4(q[4], q[5], q[6], q[7]));
-            st4(d + 8, make_float4(q[8], q[9], q[10], q[11]));
-        }
-        if (pool_midx != nullptr) {
-            uint32_t m = *reinterpret_cast<const uint32_t*>(pool_midx + s * hw + sp);
-            if (f) m = __builtin_bswap32(m);
-            float* d = out_mask + (o + p0) * c;
-            if (c == 4) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int k = (int)((m >> (8 * j)) & 0xffu);
-                    st4(d + 4 * j, make_float4(k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f, k == 3 ? 1.f : 0.f));
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int k = (int)((m >> (8 * j)) & 0xffu);
-                    for (int t = 0; t < c; ++t) d[j * c + t] = k == t ? 1.f : 0.f;
-                }
-            }
-        }
+// ---------------------------------------------------------------- cast + one-hot (read_and_encode's tensor part)
+// one one-hot row: c floats, a 1 at class k (k >= c: none); c == 4 and a 16-byte aligned row is one float4 store
+__device__ __forceinline__ void store_onehot(float* d, int k, int c) {
+    if (c == 4 && ((uintptr_t)d & 15) == 0) {
+        st4(d, make_float4(k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f, k == 3 ? 1.f : 0.f));
     } else {
-        const int p = blockIdx.x * 256 + threadIdx.x;
-        if (p >= hw) return;
-        const int y = p / w, x = p - y * w;
-        const int sp = y * w + (f ? w - 1 - x : x);
-        if (pool_img != nullptr) {
-            const uint8_t* r = pool_img + (s * hw + sp) * 3;
-            float* d = out_img + (o + p) * 3;
-            d[0] = (float)r[0]; d[1] = (float)r[1]; d[2] = (float)r[2];
-        }
-        if (pool_midx != nullptr) {
-            const int k = pool_midx[s * hw + sp];
-            float* d = out_mask + (o + p) * c;
-            for (int t = 0; t < c; ++t) d[t] = k == t ? 1.f : 0.f;
-        }
+        for (int t = 0; t < c; ++t) d[t] = k == t ? 1.f : 0.f;
     }
 }
 
-// ssdseg_rgb_augment's passes 1 and 3 on gathered samples: the same block bodies on the same pixels, so the same partial sums,
-// the same means (pass 2 is rgb_aug_means_kernel itself, once for the batch) and the same output bits
-template <bool VEC>
-__global__ void __launch_bounds__(AUG_THREADS) gather_rgb_stats_kernel(const uint8_t* __restrict__ pool_img, gather_sel sel, float* __restrict__ part,
-                                                                        int n0, int hw, float hue, float sat) {
-    const int n = blockIdx.y;
-    rgb_aug_stats_block<VEC>(pool_img + (long long)sel.index[n] * hw * 3, part + ((long long)(n0 + n) * gridDim.x + blockIdx.x) * 3, hw, hue, sat);
+// one thread per OUTPUT pixel: 3 + 1 bytes in, 3 + c floats out (c <= 8); mirrored, its source is pixel w - 1 - x of its row.
+// Either half may be NULL.  (No four-pixel form: with dword loads and 3 + c float4 stores per thread this pass measured 0.105 ms
+// at 32 x 480 x 640, c = 4, against 0.075 ms for this one, where the stores of a wave are contiguous.)
+template <typename SEL>
+__global__ void __launch_bounds__(256) expand_kernel(const uint8_t* __restrict__ src_img, const uint8_t* __restrict__ src_midx, SEL sel,
+                                                     float* __restrict__ out_img, float* __restrict__ out_mask, int n0, int h, int w, int c) {
+    const int n = blockIdx.y, hw = h * w;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= hw) return;
+    const int y = p / w, x = p - y * w;
+    const long long s = sel.source(n0, n) * hw + y * w + (sel.mirrored(n0, n) ? w - 1 - x : x);      // source pixel
+    const long long o = (long long)(n0 + n) * hw + p;                                                // output pixel
+    if (src_img != nullptr) {
+        const uint8_t* r = src_img + s * 3;
+        float* d = out_img + o * 3;
+        d[0] = (float)r[0]; d[1] = (float)r[1]; d[2] = (float)r[2];
+    }
+    if (src_midx != nullptr) store_onehot(out_mask + o * c, src_midx[s], c);
 }
 
-template <bool VEC>
-__global__ void __launch_bounds__(AUG_THREADS) gather_rgb_apply_kernel(const uint8_t* __restrict__ pool_img, gather_sel sel,
-                                                                        const float* __restrict__ means, float* __restrict__ out, int n0, int h, int w,
-                                                                        float hue, float sat, float con, float bri) {
-    const int n = blockIdx.y;
-    rgb_aug_apply_block<VEC>(pool_img + (long long)sel.index[n] * h * w * 3, out + (long long)(n0 + n) * h * w * 3, means + (n0 + n) * 3,
-                             ((sel.flip >> n) & 1ull) != 0, h, w, hue, sat, con, bri);
-}
-
-// ground-truth rows and counts of the gathered samples; rows g < count of a flagged sample mirrored as flip_gt_boxes_kernel does,
-// rows past the count zero
+// ground-truth rows and counts of gathered samples: every row written -- rows g < count of a flagged sample mirrored as
+// flip_gt_boxes_kernel does, rows past the count zero
 __global__ void __launch_bounds__(64) gather_gt_kernel(const float* __restrict__ pool_gt, const int32_t* __restrict__ pool_cnt, gather_sel sel,
                                                        float* __restrict__ gt, int32_t* __restrict__ gt_count, int n0, int gmax, float width) {
     const int n = blockIdx.y, g = blockIdx.x * 64 + threadIdx.x;
     if (g >= gmax) return;
-    const long long s = sel.index[n];
-    const bool f = ((sel.flip >> n) & 1ull) != 0;
+    const long long s = sel.source(n0, n);
     const int cnt = pool_cnt[s];
     if (g == 0) gt_count[n0 + n] = cnt;
     const float* r = pool_gt + (s * gmax + g) * 5;             // (label, xmin, ymin, xmax, ymax)
     float* o = gt + ((long long)(n0 + n) * gmax + g) * 5;
     if (g < cnt) {
-        const float xmin = r[1], xmax = r[3];
-        o[0] = r[0];
-        o[1] = f ? width - xmax : xmin;
-        o[2] = r[2];
-        o[3] = f ? width - xmin : xmax;
-        o[4] = r[4];
+        float xmin = r[1], xmax = r[3];
+        if (sel.mirrored(n0, n)) mirror_box(width, xmin, xmax);
+        o[0] = r[0]; o[1] = xmin; o[2] = r[2]; o[3] = xmax; o[4] = r[4];
     } else {
         o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; o[4] = 0.f;
     }
 }
 
-// samples [n0, n0 + count) of the host lists as one kernel-argument block
-gather_sel make_sel(const int32_t* index_host, const uint8_t* flip_host, int n0, int count) {
-    gather_sel sel;
-    memset(&sel, 0, sizeof(sel));
-    for (int i = 0; i < count; ++i) {
-        sel.index[i] = index_host[n0 + i];
-        if (flip_host != nullptr && flip_host[n0 + i] != 0) sel.flip |= 1ull << i;
-    }
-    return sel;
+// ---------------------------------------------------------------- host: each pass once, for either kind of batch
+// `make(n0, count)` gives the selection (batch_sel.h) of output samples [n0, n0 + count); its type says how many one launch takes
+
+template <typename MAKE>
+int expand_pass(ssdseg_ctx* ctx, const uint8_t* src_img, const uint8_t* src_midx, MAKE make, float* out_img, float* out_mask, int b, int h, int w,
+                int c) {
+    using SEL = decltype(make(0, 0));
+    const int hw = h * w;
+    return for_each_chunk(b, SEL::chunk, [&](int n0, int count) {
+        const double bytes = (double)count * hw * ((src_img ? 3.0 + 12.0 : 0.0) + (src_midx ? 1.0 + 4.0 * c : 0.0));
+        SSDSEG_LAUNCH_NAMED(ctx, "expand_kernel", bytes, 0.0, expand_kernel<SEL>, dim3(cdiv(hw, 256), count), dim3(256), 0, src_img, src_midx,
+                            make(n0, count), out_img, out_mask, n0, h, w, c);
+        return launch_status("expand_kernel");
+    });
 }
 
-bool indices_in_pool(const int32_t* index_host, int b, int n_pool) {
-    for (int i = 0; i < b; ++i)
-        if (index_host[i] < 0 || index_host[i] >= n_pool) return false;
-    return true;
+// the three colour passes; the block partials of pass 1 live in the ctx workspace
+template <typename MAKE>
+int rgb_passes(ssdseg_ctx* ctx, const uint8_t* src_img, MAKE make, const float* draws4, float* means, float* out, int b, int h, int w) {
+    using SEL = decltype(make(0, 0));
+    // dword pixel loads and float4 stores: whole groups of 4 pixels per row and aligned buffers
+    const bool vec = w % AUG_PIX == 0 && ((uintptr_t)src_img & 3) == 0 && ((uintptr_t)out & 15) == 0;
+    const float hue = draws4[0], sat = draws4[1], con = draws4[2], bri = draws4[3];
+    const int hw = h * w, nb = cdiv(hw, AUG_BLOCK_PIX);
+    void* ws = nullptr;
+    int rc = ssdseg_workspace(ctx, (size_t)b * nb * 3 * sizeof(float), &ws);
+    if (rc) return rc;
+    float* part = static_cast<float*>(ws);
+    rc = for_each_chunk(b, SEL::chunk, [&](int n0, int count) {
+        return launch_vec<rgb_stats_kernel<true, SEL>, rgb_stats_kernel<false, SEL>>(ctx, vec, "rgb_stats_kernel", 3.0 * count * hw + 12.0 * count * nb,
+                                                                                    dim3(nb, count), AUG_THREADS, src_img, make(n0, count), part, n0, hw,
+                                                                                    hue, sat);
+    });
+    if (rc) return rc;
+    rc = for_each_chunk(b, GRID_Y_MAX, [&](int n0, int count) {                 // one grid row per image
+        SSDSEG_LAUNCH(ctx, 12.0 * count * nb + 12.0 * count, 0.0, rgb_aug_means_kernel, dim3(3, count), dim3(64), 0, part + (size_t)n0 * nb * 3,
+                      means + (size_t)n0 * 3, nb, hw);
+        return launch_status("rgb_aug_means_kernel");
+    });
+    if (rc) return rc;
+    return for_each_chunk(b, SEL::chunk, [&](int n0, int count) {
+        return launch_vec<rgb_apply_kernel<true, SEL>, rgb_apply_kernel<false, SEL>>(ctx, vec, "rgb_apply_kernel", 15.0 * count * hw + 12.0 * count,
+                                                                                    dim3(nb, count), AUG_THREADS, src_img, make(n0, count), means, out, n0,
+                                                                                    h, w, hue, sat, con, bri);
+    });
 }
 
 }  // namespace
@@ -383,14 +331,9 @@ int ssdseg_expand_inputs(ssdseg_ctx* ctx, const uint8_t* images_u8, const uint8_
     SSDSEG_ARG(images_u8 == nullptr || images_f32 != nullptr, 5);
     SSDSEG_ARG(mask_index_u8 == nullptr || mask_onehot != nullptr, 6);
     SSDSEG_ARG(b > 0 && h > 0 && w > 0, 7);
+    SSDSEG_ARG((long long)h * w * 3 < (1LL << 31), 8);       // in-image pixel and byte offsets in 32 bits
     SSDSEG_ARG(c > 0 && c <= 8, 10);
-    const long long total = (long long)b * h * w;
-    const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    const double bytes = (double)total * ((images_u8 ? 3.0 + 12.0 : 0.0) + (mask_index_u8 ? 1.0 + 4.0 * c : 0.0));
-    SSDSEG_LAUNCH(ctx, bytes, 0.0, expand_inputs_kernel, dim3(blocks), dim3(256), 0, images_u8, mask_index_u8, flip, images_f32, mask_onehot, h, w, c,
-                  total);
-    SSDSEG_LAUNCH_CHECK();
-    return 0;
+    return expand_pass(ctx, images_u8, mask_index_u8, [=](int, int) { return plain_sel{flip}; }, images_f32, mask_onehot, b, h, w, c);
 }
 
 int ssdseg_flip_gt_boxes(ssdseg_ctx* ctx, float* gt, const int32_t* gt_count, const uint8_t* flip, int b, int gmax, float image_width) {
@@ -409,36 +352,13 @@ int ssdseg_rgb_augment(ssdseg_ctx* ctx, const uint8_t* images_u8, const uint8_t*
     SSDSEG_ARG(ctx != nullptr, 1);
     SSDSEG_ARG(images_u8 != nullptr, 2);
     SSDSEG_ARG(draws4_host != nullptr, 4);
-    SSDSEG_ARG(std::isfinite(draws4_host[0]) && std::isfinite(draws4_host[1]) && std::isfinite(draws4_host[2]) && std::isfinite(draws4_host[3]), 4);
+    SSDSEG_ARG(draws_finite(draws4_host), 4);
     SSDSEG_ARG(means != nullptr, 5);
     SSDSEG_ARG(images_f32 != nullptr, 6);
     SSDSEG_ARG(b > 0 && h > 0 && w > 0, 7);
     // one grid row per image; in-image pixel and byte offsets in 32 bits
     SSDSEG_ARG(b <= 65535 && (long long)h * w * 3 < (1LL << 31), 7);
-    const float hue = draws4_host[0], sat = draws4_host[1], con = draws4_host[2], bri = draws4_host[3];
-    const int hw = h * w, nb = cdiv(hw, AUG_BLOCK_PIX);
-    void* ws = nullptr;
-    int rc = ssdseg_workspace(ctx, (size_t)b * nb * 3 * sizeof(float), &ws);
-    if (rc) return rc;
-    float* part = static_cast<float*>(ws);
-    const double px = (double)b * hw;
-    // dword pixel loads and float4 stores: whole groups of 4 pixels per row and aligned buffers
-    const bool vec = w % AUG_PIX == 0 && ((uintptr_t)images_u8 & 3) == 0 && ((uintptr_t)images_f32 & 15) == 0;
-    if (vec)
-        SSDSEG_LAUNCH(ctx, 3.0 * px + 12.0 * b * nb, 0.0, rgb_aug_stats_kernel<true>, dim3(nb, b), dim3(AUG_THREADS), 0, images_u8, part, hw, hue, sat);
-    else
-        SSDSEG_LAUNCH(ctx, 3.0 * px + 12.0 * b * nb, 0.0, rgb_aug_stats_kernel<false>, dim3(nb, b), dim3(AUG_THREADS), 0, images_u8, part, hw, hue, sat);
-    SSDSEG_LAUNCH_CHECK();
-    SSDSEG_LAUNCH(ctx, 12.0 * b * nb + 12.0 * b, 0.0, rgb_aug_means_kernel, dim3(3, b), dim3(64), 0, part, means, nb, hw);
-    SSDSEG_LAUNCH_CHECK();
-    if (vec)
-        SSDSEG_LAUNCH(ctx, 15.0 * px + 12.0 * b, 0.0, rgb_aug_apply_kernel<true>, dim3(nb, b), dim3(AUG_THREADS), 0, images_u8, flip, means, images_f32,
-                      h, w, hue, sat, con, bri);
-    else
-        SSDSEG_LAUNCH(ctx, 15.0 * px + 12.0 * b, 0.0, rgb_aug_apply_kernel<false>, dim3(nb, b), dim3(AUG_THREADS), 0, images_u8, flip, means, images_f32,
-                      h, w, hue, sat, con, bri);
-    SSDSEG_LAUNCH_CHECK();
-    return 0;
+    return rgb_passes(ctx, images_u8, [=](int, int) { return plain_sel{flip}; }, draws4_host, means, images_f32, b, h, w);
 }
 
 int ssdseg_gather_inputs(ssdseg_ctx* ctx, const uint8_t* pool_images, const uint8_t* pool_masks, int n_pool, const int32_t* index_host,
@@ -449,77 +369,23 @@ int ssdseg_gather_inputs(ssdseg_ctx* ctx, const uint8_t* pool_images, const uint
     SSDSEG_ARG(n_pool > 0, 4);
     SSDSEG_ARG(index_host != nullptr, 5);
     SSDSEG_ARG(draws4_host == nullptr || pool_images != nullptr, 7);
-    SSDSEG_ARG(draws4_host == nullptr ||
-               (std::isfinite(draws4_host[0]) && std::isfinite(draws4_host[1]) && std::isfinite(draws4_host[2]) && std::isfinite(draws4_host[3])), 7);
+    SSDSEG_ARG(draws4_host == nullptr || draws_finite(draws4_host), 7);
     SSDSEG_ARG(draws4_host == nullptr || means != nullptr, 8);
     SSDSEG_ARG(pool_images == nullptr || images_f32 != nullptr, 9);
     SSDSEG_ARG(pool_masks == nullptr || mask_onehot != nullptr, 10);
     SSDSEG_ARG(b > 0 && h > 0 && w > 0, 11);
     SSDSEG_ARG((long long)h * w * 3 < (1LL << 31), 12);      // in-image pixel and byte offsets in 32 bits
     SSDSEG_ARG(c > 0 && c <= 8, 14);
-    SSDSEG_ARG(indices_in_pool(index_host, b, n_pool), 5);
-    const int hw = h * w;
+    SSDSEG_ARG(indices_in_source(index_host, b, n_pool), 5);
     const bool colour = draws4_host != nullptr;
-    // dword loads and float4 stores: whole groups of 4 pixels per row and aligned buffers
-    const bool vec = w % 4 == 0 && (pool_images == nullptr || (((uintptr_t)pool_images & 3) == 0 && ((uintptr_t)images_f32 & 15) == 0)) &&
-                     (pool_masks == nullptr || (((uintptr_t)pool_masks & 3) == 0 && ((uintptr_t)mask_onehot & 15) == 0));
-    const int nb = cdiv(hw, AUG_BLOCK_PIX);
-    float hue = 0.f, sat = 1.f, con = 1.f, bri = 0.f;
-    float* part = nullptr;
-    if (colour) {
-        hue = draws4_host[0]; sat = draws4_host[1]; con = draws4_host[2]; bri = draws4_host[3];
-        void* ws = nullptr;
-        int rc = ssdseg_workspace(ctx, (size_t)b * nb * 3 * sizeof(float), &ws);
-        if (rc) return rc;
-        part = static_cast<float*>(ws);
-    }
+    const auto make = [=](int n0, int count) { return make_sel(index_host, flip_host, n0, count); };
     // the plain expansion: both halves, or only the mask when the image comes from the colour passes
     const uint8_t* ex_img = colour ? nullptr : pool_images;
     if (ex_img != nullptr || pool_masks != nullptr) {
-        const int gx = vec ? cdiv(hw, 1024) : cdiv(hw, 256);
-        for (int n0 = 0; n0 < b; n0 += GATHER_CHUNK) {
-            const int count = b - n0 < GATHER_CHUNK ? b - n0 : GATHER_CHUNK;
-            const gather_sel sel = make_sel(index_host, flip_host, n0, count);
-            const double bytes = (double)count * hw * ((ex_img ? 3.0 + 12.0 : 0.0) + (pool_masks ? 1.0 + 4.0 * c : 0.0));
-            if (vec)
-                SSDSEG_LAUNCH(ctx, bytes, 0.0, gather_expand_kernel<true>, dim3(gx, count), dim3(256), 0, ex_img, pool_masks, sel, images_f32, mask_onehot,
-                              n0, h, w, c);
-            else
-                SSDSEG_LAUNCH(ctx, bytes, 0.0, gather_expand_kernel<false>, dim3(gx, count), dim3(256), 0, ex_img, pool_masks, sel, images_f32,
-                              mask_onehot, n0, h, w, c);
-            SSDSEG_LAUNCH_CHECK();
-        }
+        const int rc = expand_pass(ctx, ex_img, pool_masks, make, images_f32, mask_onehot, b, h, w, c);
+        if (rc) return rc;
     }
-    if (!colour) return 0;
-    for (int n0 = 0; n0 < b; n0 += GATHER_CHUNK) {
-        const int count = b - n0 < GATHER_CHUNK ? b - n0 : GATHER_CHUNK;
-        const gather_sel sel = make_sel(index_host, nullptr, n0, count);       // the mean ignores the mirror
-        const double bytes = 3.0 * count * hw + 12.0 * count * nb;
-        if (vec)
-            SSDSEG_LAUNCH(ctx, bytes, 0.0, gather_rgb_stats_kernel<true>, dim3(nb, count), dim3(AUG_THREADS), 0, pool_images, sel, part, n0, hw, hue, sat);
-        else
-            SSDSEG_LAUNCH(ctx, bytes, 0.0, gather_rgb_stats_kernel<false>, dim3(nb, count), dim3(AUG_THREADS), 0, pool_images, sel, part, n0, hw, hue, sat);
-        SSDSEG_LAUNCH_CHECK();
-    }
-    for (int n0 = 0; n0 < b; n0 += 65535) {                                     // one grid row per image
-        const int count = b - n0 < 65535 ? b - n0 : 65535;
-        SSDSEG_LAUNCH(ctx, 12.0 * count * nb + 12.0 * count, 0.0, rgb_aug_means_kernel, dim3(3, count), dim3(64), 0, part + (size_t)n0 * nb * 3,
-                      means + (size_t)n0 * 3, nb, hw);
-        SSDSEG_LAUNCH_CHECK();
-    }
-    for (int n0 = 0; n0 < b; n0 += GATHER_CHUNK) {
-        const int count = b - n0 < GATHER_CHUNK ? b - n0 : GATHER_CHUNK;
-        const gather_sel sel = make_sel(index_host, flip_host, n0, count);
-        const double bytes = 15.0 * count * hw + 12.0 * count;
-        if (vec)
-            SSDSEG_LAUNCH(ctx, bytes, 0.0, gather_rgb_apply_kernel<true>, dim3(nb, count), dim3(AUG_THREADS), 0, pool_images, sel, means, images_f32, n0,
-                          h, w, hue, sat, con, bri);
-        else
-            SSDSEG_LAUNCH(ctx, bytes, 0.0, gather_rgb_apply_kernel<false>, dim3(nb, count), dim3(AUG_THREADS), 0, pool_images, sel, means, images_f32, n0,
-                          h, w, hue, sat, con, bri);
-        SSDSEG_LAUNCH_CHECK();
-    }
-    return 0;
+    return colour ? rgb_passes(ctx, pool_images, make, draws4_host, means, images_f32, b, h, w) : 0;
 }
 
 int ssdseg_gather_gt(ssdseg_ctx* ctx, const float* pool_gt, const int32_t* pool_cnt, int n_pool, const int32_t* index_host,
@@ -532,15 +398,12 @@ int ssdseg_gather_gt(ssdseg_ctx* ctx, const float* pool_gt, const int32_t* pool_
     SSDSEG_ARG(gt != nullptr, 7);
     SSDSEG_ARG(gt_count != nullptr, 8);
     SSDSEG_ARG(b > 0 && gmax > 0, 9);
-    SSDSEG_ARG(indices_in_pool(index_host, b, n_pool), 5);
-    for (int n0 = 0; n0 < b; n0 += GATHER_CHUNK) {
-        const int count = b - n0 < GATHER_CHUNK ? b - n0 : GATHER_CHUNK;
-        const gather_sel sel = make_sel(index_host, flip_host, n0, count);
-        SSDSEG_LAUNCH(ctx, (40.0 * gmax + 8.0) * count, 0.0, gather_gt_kernel, dim3(cdiv(gmax, 64), count), dim3(64), 0, pool_gt, pool_cnt, sel, gt,
-                      gt_count, n0, gmax, image_width);
-        SSDSEG_LAUNCH_CHECK();
-    }
-    return 0;
+    SSDSEG_ARG(indices_in_source(index_host, b, n_pool), 5);
+    return for_each_chunk(b, gather_sel::chunk, [&](int n0, int count) {
+        SSDSEG_LAUNCH(ctx, (40.0 * gmax + 8.0) * count, 0.0, gather_gt_kernel, dim3(cdiv(gmax, 64), count), dim3(64), 0, pool_gt, pool_cnt,
+                      make_sel(index_host, flip_host, n0, count), gt, gt_count, n0, gmax, image_width);
+        return launch_status("gather_gt_kernel");
+    });
 }
 
 }  // extern "C"

@@ -37,6 +37,14 @@ def test_argument_errors_do_not_need_a_device(lib):
     assert b"invalid argument 4" in lib.ssdseg_last_error()
     assert lib.ssdseg_pwconv_parts(640, 96, C.byref(out)) == 0 and out.value == 5
     assert lib.ssdseg_stem_conv_parts(2, 480, 640, 32, C.byref(out)) == 0 and out.value > 0
+    # ssdseg_expand_inputs: in-image offsets are 32-bit, so an image of 2^31 bytes or more is refused -- after the pointer and
+    # size checks, before the ctx or any buffer is touched (stand-ins that are never dereferenced)
+    ctx, buf = C.create_string_buffer(8), C.create_string_buffer(8)
+    h, w = 32768, 21846
+    assert h * w * 3 >= 1 << 31 > h * (w - 1) * 3
+    assert lib.ssdseg_expand_inputs(ctx, buf, None, None, buf, None, 1, h, w, 4) == -1000 - 8
+    assert b"ssdseg_expand_inputs: invalid argument 8" in lib.ssdseg_last_error()
+    assert lib.ssdseg_expand_inputs(ctx, buf, None, None, buf, None, 1, h, w - 1, 9) == -1000 - 10     # the largest image passes that check
 
 
 # Dispatch switches the forward entry points read at LAUNCH time, with the values the parity tests give them (None: unset)

@@ -8,7 +8,7 @@ import pytest
 
 from oracle import np_ops as O
 from tests.test_gpu_full_model import CW, SHAPE, build, make_targets
-from _guard import guards  # noqa: F401  (fixture)
+from _guard import BODY_WORD, guards  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,6 +32,103 @@ def test_expand_inputs_bit_exact(ctx, guards, rng, b, h, w, c, with_flip):
     ctx.call("ssdseg_expand_inputs", None, guards.inp(idx, dtype=np.uint8), d_flip, None, d_mask, b, h, w, c)
     np.testing.assert_array_equal(d_img.download(), want_img)
     np.testing.assert_array_equal(d_mask.download(), want_mask)
+
+
+B_BLOCKS = 130                          # two full 64-sample kernel-argument blocks (csrc/batch_sel.h) and two samples
+BLOCK_SHAPES = [(2, 8, 4), (2, 8, 3), (3, 5, 4), (3, 5, 3)]      # (h, w, c): four pixels per thread in the colour kernels / one; float4 one-hot rows / loops
+
+
+def _block_flags(rng):
+    """flip flags of B_BLOCKS samples that differ across both block edges"""
+    flip = rng.integers(0, 2, B_BLOCKS).astype(np.uint8)
+    flip[[63, 64, 127, 128]] = [1, 0, 0, 1]
+    return flip
+
+
+@pytest.mark.parametrize("h,w,c", BLOCK_SHAPES)
+def test_expand_inputs_of_130_samples(ctx, guards, rng, h, w, c):
+    """a plain batch has no 64-sample block: more samples than one block holds, flags from the device array"""
+    b = B_BLOCKS
+    img = rng.integers(0, 256, (b, h, w, 3)).astype(np.uint8)
+    idx = rng.integers(0, c + 2, (b, h, w)).astype(np.uint8)
+    flip = _block_flags(rng)
+    want_img, want_mask = O.expand_inputs(img, idx, flip, c)
+    d_img, d_mask = guards.out((b, h, w, 3)), guards.out((b, h, w, c))
+    ctx.call("ssdseg_expand_inputs", guards.inp(img, dtype=np.uint8), guards.inp(idx, dtype=np.uint8), guards.inp(flip, dtype=np.uint8), d_img, d_mask,
+             b, h, w, c)
+    np.testing.assert_array_equal(d_img.download(), want_img)
+    np.testing.assert_array_equal(d_mask.download(), want_mask)
+    guards.check()
+
+
+PLACEMENTS = ["image source", "class-index source", "image destination", "one-hot destination"]
+ODD_SHAPE = (2, 3, 8, 4)                # (b, h, w, c): the width allows four pixels per thread, c a float4 per one-hot row; a shifted buffer does not
+
+
+class Shifted:
+    """the buffers of one call with ONE of them off its alignment: a uint8 source one byte, or a float destination one float,
+    into a guarded allocation (dword loads / float4 stores there would fault or hit the wrong bytes).  `b`: the sources are
+    pools, the outputs a batch of b; idx / c None: the call takes no class indices."""
+
+    def __init__(self, guards, img, idx, which, b=None, c=None):
+        assert which in PLACEMENTS
+        shape = (len(img) if b is None else b,) + img.shape[1:]
+        self.img = self._source(guards, img, which == "image source")
+        self.idx = self._source(guards, idx, which == "class-index source") if idx is not None else None
+        self._img_whole, self.out = self._destination(guards, shape, which == "image destination")
+        if c is not None:
+            self._mask_whole, self.mask_out = self._destination(guards, shape[:3] + (c,), which == "one-hot destination")
+
+    @staticmethod
+    def _source(guards, a, shifted):
+        if not shifted:
+            return guards.inp(a, dtype=np.uint8)
+        return guards.inp(np.concatenate([[0], a.ravel(), [0] * 7]), dtype=np.uint8).view(1, a.shape)
+
+    @staticmethod
+    def _destination(guards, shape, shifted):
+        """(the allocation a shifted view lies in or None, the buffer to hand to the call)"""
+        if not shifted:
+            return None, guards.out(shape)
+        whole = guards.out((int(np.prod(shape)) + 4,))
+        return whole, whole.view(1, shape)
+
+    @staticmethod
+    def _body(whole, out):
+        """what the call wrote; around a shifted destination the poison must be intact"""
+        if whole is None:
+            return out.download()
+        raw, n = whole.download(), out.size
+        assert (np.concatenate([raw[:1], raw[1 + n:]]).view(np.uint32) == BODY_WORD).all()
+        return raw[1:1 + n].reshape(out.shape)
+
+    def image(self):
+        return self._body(self._img_whole, self.out)
+
+    def mask(self):
+        return self._body(self._mask_whole, self.mask_out)
+
+    def repoison(self, guards):
+        for whole, out in ((self._img_whole, self.out), (getattr(self, "_mask_whole", None), getattr(self, "mask_out", None))):
+            if out is not None:
+                guards.repoison(whole if whole is not None else out)
+
+
+@pytest.mark.parametrize("which", PLACEMENTS)
+def test_expand_inputs_falls_back_on_a_misaligned_buffer(ctx, guards, rng, which):
+    b, h, w, c = ODD_SHAPE
+    img = rng.integers(0, 256, (b, h, w, 3)).astype(np.uint8)
+    idx = rng.integers(0, c + 2, (b, h, w)).astype(np.uint8)
+    flip = np.array([1, 0], np.uint8)
+    want_img, want_mask = O.expand_inputs(img, idx, flip, c)
+    d_flip = guards.inp(flip, dtype=np.uint8)
+    a_img, a_mask = guards.out((b, h, w, 3)), guards.out((b, h, w, c))
+    ctx.call("ssdseg_expand_inputs", guards.inp(img, dtype=np.uint8), guards.inp(idx, dtype=np.uint8), d_flip, a_img, a_mask, b, h, w, c)
+    s = Shifted(guards, img, idx, which, c=c)
+    ctx.call("ssdseg_expand_inputs", s.img, s.idx, d_flip, s.out, s.mask_out, b, h, w, c)
+    assert s.image().tobytes() == a_img.download().tobytes() == want_img.tobytes()
+    assert s.mask().tobytes() == a_mask.download().tobytes() == want_mask.tobytes()
+    guards.check()
 
 
 def test_expand_inputs_rejects_bad_arguments(ctx, guards):
@@ -63,6 +160,24 @@ def test_flip_gt_boxes_bit_exact(ctx, guards, rng):
     d = guards.out(gt.shape).upload(gt)     # flipped in place
     ctx.call("ssdseg_flip_gt_boxes", d, guards.inp(cnt, dtype=np.int32), guards.inp(flip, dtype=np.uint8), b, gmax, width)
     np.testing.assert_array_equal(d.download(), want)       # rows past the count and unflagged samples untouched
+
+
+def test_flip_gt_boxes_of_130_samples(ctx, guards, rng):
+    b, gmax, width = B_BLOCKS, 4, 640.0
+    cnt = rng.integers(0, gmax + 1, b).astype(np.int32)
+    cnt[[63, 64, 127, 128]] = gmax
+    gt = np.zeros((b, gmax, 5), np.float32)
+    for n in range(b):
+        x0 = rng.uniform(0, 500, cnt[n]); x1 = x0 + rng.uniform(1, 139, cnt[n])
+        gt[n, :cnt[n]] = np.stack([rng.integers(1, 4, cnt[n]), x0, rng.uniform(0, 400, cnt[n]), x1, rng.uniform(400, 479, cnt[n])], axis=1)
+    flip = _block_flags(rng)
+    want = gt.copy()
+    for n in range(b):
+        if flip[n]:
+            want[n, :cnt[n]] = O.flip_gt_boxes(gt[n, :cnt[n]], width)
+    d = guards.out(gt.shape).upload(gt)     # flipped in place
+    ctx.call("ssdseg_flip_gt_boxes", d, guards.inp(cnt, dtype=np.int32), guards.inp(flip, dtype=np.uint8), b, gmax, width)
+    np.testing.assert_array_equal(d.download(), want)
 
 
 def _compile(model):

@@ -11,8 +11,8 @@ import pytest
 
 from oracle import np_ops as O
 from tests.test_gpu_full_model import SHAPE, build
-from tests.test_gpu_input_pipeline import _compact_batches, _compile
-from tests.test_gpu_rgb_augmentation import CLAMP, HIGH, LOW, _f32, _pixels
+from tests.test_gpu_input_pipeline import B_BLOCKS, BLOCK_SHAPES, ODD_SHAPE, PLACEMENTS, Shifted, _block_flags, _compact_batches, _compile
+from tests.test_gpu_rgb_augmentation import CLAMP, HIGH, LOW, _f32, _host as _host_spec, _pixels, _tolerance
 from _guard import guards  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -110,6 +110,97 @@ def test_gather_gt_bit_exact(ctx, guards, rng):
         assert all(not got[n, cnt[s]:].any() for n, s in enumerate(index))      # rows past the count are zeros
         guards.check()
         guards.repoison(d_gt); guards.repoison(d_cnt)
+
+
+POOL_BLOCKS = 9
+
+
+def _block_lists(rng):
+    """index list and flags of B_BLOCKS samples: both ends of the pool on either side of both 64-sample block edges and at the
+    end of the list, flags that differ across the edges"""
+    index = rng.integers(0, POOL_BLOCKS, B_BLOCKS).astype(np.int32)
+    index[[0, 63, 64, 127, 128, 129]] = [8, 0, 8, 0, 8, 0]
+    return index, _block_flags(rng)
+
+
+@pytest.mark.parametrize("h,w,c", BLOCK_SHAPES)
+def test_gather_inputs_across_argument_blocks(ctx, guards, rng, h, w, c):
+    b = B_BLOCKS
+    img = _pixels(rng, POOL_BLOCKS, h, w)
+    idx = rng.integers(0, c + 2, (POOL_BLOCKS, h, w)).astype(np.uint8)
+    index, flip = _block_lists(rng)
+    p_img, p_idx = guards.inp(img, dtype=np.uint8), guards.inp(idx, dtype=np.uint8)
+    d_img, d_mask = guards.out((b, h, w, 3)), guards.out((b, h, w, c))
+    want_img, want_mask = O.expand_inputs(img[index], idx[index], flip, c)
+    _gather_inputs(ctx, p_img, p_idx, POOL_BLOCKS, index, flip, None, None, d_img, d_mask, b, h, w, c)
+    np.testing.assert_array_equal(d_img.download(), want_img)
+    np.testing.assert_array_equal(d_mask.download(), want_mask)
+    guards.check()
+    guards.repoison(d_img); guards.repoison(d_mask)
+    # the colour form: the merged entry point on the host-stacked samples byte for byte, and the host spec within its bound
+    draws = _f32(HIGH)
+    want_means, want_aug = guards.out((b, 3)), guards.out((b, h, w, 3))
+    ctx.call("ssdseg_rgb_augment", guards.inp(img[index], dtype=np.uint8), guards.inp(flip, dtype=np.uint8), (C.c_float * 4)(*draws), want_means,
+             want_aug, b, h, w)
+    means = guards.out((b, 3))
+    _gather_inputs(ctx, p_img, p_idx, POOL_BLOCKS, index, flip, draws, means, d_img, d_mask, b, h, w, c)
+    assert means.download().tobytes() == want_means.download().tobytes()
+    assert d_img.download().tobytes() == want_aug.download().tobytes()
+    np.testing.assert_array_equal(d_mask.download(), want_mask)
+    guards.check()
+    spec, m64, m32 = _host_spec(img[index], flip, draws)
+    np.testing.assert_allclose(means.download(), m64, rtol=1e-5)
+    err = float(np.abs(d_img.download() - spec).max())
+    assert err <= _tolerance(draws, m64, m32), (err, _tolerance(draws, m64, m32))
+
+
+def test_gather_gt_across_argument_blocks(ctx, guards, rng):
+    gmax, width, b = 4, 640.0, B_BLOCKS
+    cnt = np.array([gmax, 0, 3, 2, 1, gmax, 0, 2, 3], np.int32)
+    gt = np.full((POOL_BLOCKS, gmax, 5), 7.0, np.float32)       # rows past the count hold something a stale copy would show
+    for s in range(POOL_BLOCKS):
+        x0 = rng.uniform(0, 500, cnt[s]); x1 = x0 + rng.uniform(1, 139, cnt[s])
+        gt[s, :cnt[s]] = np.stack([rng.integers(1, 4, cnt[s]), x0, rng.uniform(0, 400, cnt[s]), x1, rng.uniform(400, 479, cnt[s])], axis=1)
+    index, flip = _block_lists(rng)
+    want = np.zeros((b, gmax, 5), np.float32)
+    for n, s in enumerate(index):
+        rows = gt[s, :cnt[s]]
+        want[n, :cnt[s]] = O.flip_gt_boxes(rows, width) if flip[n] else rows
+    d_gt, d_cnt = guards.out((b, gmax, 5)), guards.out((b,), np.int32)
+    _gather_gt(ctx, guards.inp(gt), guards.inp(cnt, dtype=np.int32), POOL_BLOCKS, index, flip, d_gt, d_cnt, b, gmax, width)
+    np.testing.assert_array_equal(d_cnt.download(), cnt[index])
+    got = d_gt.download()
+    np.testing.assert_array_equal(got, want)
+    assert all(not got[n, cnt[s]:].any() for n, s in enumerate(index))      # rows past the count are zeros
+    guards.check()
+
+
+@pytest.mark.parametrize("which", PLACEMENTS)
+def test_gather_inputs_falls_back_on_a_misaligned_buffer(ctx, guards, rng, which):
+    """both forms; the pools are the shifted sources"""
+    b, h, w, c = ODD_SHAPE
+    img = _pixels(rng, N_POOL, h, w)
+    idx = rng.integers(0, c + 2, (N_POOL, h, w)).astype(np.uint8)
+    index, flip = np.array([4, 0], np.int32), np.array([1, 0], np.uint8)
+    want_img, want_mask = O.expand_inputs(img[index], idx[index], flip, c)
+    p_img, p_idx = guards.inp(img, dtype=np.uint8), guards.inp(idx, dtype=np.uint8)
+    a_means, a_img, a_mask = guards.out((b, 3)), guards.out((b, h, w, 3)), guards.out((b, h, w, c))
+    s, means = Shifted(guards, img, idx, which, b, c), guards.out((b, 3))
+    _gather_inputs(ctx, p_img, p_idx, N_POOL, index, flip, None, None, a_img, a_mask, b, h, w, c)
+    _gather_inputs(ctx, s.img, s.idx, N_POOL, index, flip, None, None, s.out, s.mask_out, b, h, w, c)
+    assert s.image().tobytes() == a_img.download().tobytes() == want_img.tobytes()
+    assert s.mask().tobytes() == a_mask.download().tobytes() == want_mask.tobytes()
+    guards.check()
+    s.repoison(guards); guards.repoison(a_img); guards.repoison(a_mask)
+    draws = _f32(HIGH)
+    _gather_inputs(ctx, p_img, p_idx, N_POOL, index, flip, draws, a_means, a_img, a_mask, b, h, w, c)
+    _gather_inputs(ctx, s.img, s.idx, N_POOL, index, flip, draws, means, s.out, s.mask_out, b, h, w, c)
+    assert s.image().tobytes() == a_img.download().tobytes() and means.download().tobytes() == a_means.download().tobytes()
+    assert s.mask().tobytes() == a_mask.download().tobytes() == want_mask.tobytes()
+    guards.check()
+    spec, m64, m32 = _host_spec(img[index], flip, draws)
+    np.testing.assert_allclose(a_means.download(), m64, rtol=1e-5)
+    assert float(np.abs(a_img.download() - spec).max()) <= _tolerance(draws, m64, m32)
 
 
 def test_gather_rejects_bad_arguments_before_anything_is_written(ctx, guards):

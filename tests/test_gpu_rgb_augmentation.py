@@ -8,7 +8,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests.test_gpu_input_pipeline import _compact_batches, _compile, _device_encoded
+from tests.test_gpu_input_pipeline import (B_BLOCKS, BLOCK_SHAPES, ODD_SHAPE, PLACEMENTS, Shifted, _block_flags, _compact_batches, _compile,
+                                           _device_encoded)
 from tests.test_gpu_full_model import build
 from _guard import guards  # noqa: F401  (fixture)
 
@@ -127,6 +128,43 @@ def test_rgb_augment_matches_the_host_spec(ctx, guards, rng, shape, draws):
         err = float(np.abs(got - w).max())
         assert err <= tol, (shape, draws, f is not None, err, tol)
         assert got.min() >= 0.0 and got.max() <= 255.0
+
+
+def _tolerance(draws, m64, m32):
+    """the bound of test_rgb_augment_matches_the_host_spec: ATOL plus what the float32 mean of the host spec moves the output"""
+    return ATOL + abs(1.0 - draws[2]) * float(np.abs(m32 - m64).max())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("h,w", sorted({s[:2] for s in BLOCK_SHAPES}))
+def test_rgb_augment_of_130_samples(ctx, guards, rng, h, w):
+    """a plain batch has no 64-sample block: more samples than one block holds, flags from the device array"""
+    draws = _f32(HIGH)
+    img = _pixels(rng, B_BLOCKS, h, w)
+    flip = _block_flags(rng)
+    want, m64, m32 = _host(img, flip, draws)
+    got, means = _device(ctx, guards, img, flip, draws)
+    guards.check()
+    np.testing.assert_allclose(means, m64, rtol=1e-5)
+    err = float(np.abs(got - want).max())
+    assert err <= _tolerance(draws, m64, m32), (err, _tolerance(draws, m64, m32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", [p for p in PLACEMENTS if p.startswith("image")])       # the call takes no class indices
+def test_rgb_augment_falls_back_on_a_misaligned_buffer(ctx, guards, rng, which):
+    b, h, w, _ = ODD_SHAPE
+    draws = _f32(HIGH)
+    img = _pixels(rng, b, h, w)
+    flip = np.array([1, 0], np.uint8)
+    want, m64, m32 = _host(img, flip, draws)
+    a_img, a_means = _device(ctx, guards, img, flip, draws)
+    s, means = Shifted(guards, img, None, which), guards.out((b, 3))
+    ctx.call("ssdseg_rgb_augment", s.img, guards.inp(flip, dtype=np.uint8), (C.c_float * 4)(*draws), means, s.out, b, h, w)
+    assert s.image().tobytes() == a_img.tobytes() and means.download().tobytes() == a_means.tobytes()
+    guards.check()
+    np.testing.assert_allclose(a_means, m64, rtol=1e-5)
+    assert float(np.abs(a_img - want).max()) <= _tolerance(draws, m64, m32)
 
 
 @pytest.mark.gpu
