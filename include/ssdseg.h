@@ -330,7 +330,12 @@ int ssdseg_bilinear_fwd_padded(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, 
 /* ---------------------------------------------------------------- K12+K13: mask head tail
  * logits [n][h][w][c] --x(fy,fx) bilinear--> softmax -> probabilities (output-mask, blocks.py:128-130),
  * optionally fused with the weighted cross-entropy (losses.py:294-303): loss[n] = -sum_c w_c sum_px y*log(clip p).
- * prob may be NULL (training does not need it stored); y_true/loss may be NULL (inference). */
+ * prob may be NULL (training does not need it stored); y_true/loss may be NULL (inference).  n <= 65535 (the image is a grid
+ * dimension of the forward kernels; the same holds for ssdseg_mask_head_fwd_dice and ssdseg_mask_head_fwd_bootstrap).
+ * The clip interval is [lo, hi] in float32: lo = float(1e-7), hi = 1.f - float(1e-7) = 1 - 2^-23 (NOT 1 - 1e-7, which float32
+ * does not have).  The loss takes log(min(max(p, lo), hi)).  The gradient follows the clip: a labelled (pixel, class) entry whose
+ * probability is outside [lo, hi] contributes a zero dL/dp, so a pixel whose labelled probabilities are all outside has an
+ * exactly zero row of d loss / d logits; inside, dL/dp_c = -w_c y_c / p_c. */
 int ssdseg_mask_head_fwd(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx,
                          const float* y_true, const float* class_weights_host, float* prob, float* loss);
 /* dlogits (low resolution) = upsample^T( softmax'( dL/dp ) ), dL/dp = -loss_scale * w_c * y / p inside the clip */

@@ -545,6 +545,7 @@ extern "C" {
 int ssdseg_mask_head_fwd(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx, const float* y_true,
                          const float* class_weights_host, float* prob, float* loss) {
     MASK_HEAD_ARGS();
+    SSDSEG_ARG(n <= 65535, 3);   // the image is gridDim.y of mask_head_fwd_kernel
     SSDSEG_ARG((loss == nullptr) || (y_true != nullptr && class_weights_host != nullptr), 9);
     const float zero[4] = {0.f, 0.f, 0.f, 0.f};
     const long long npix = (long long)h * fy * wdt * fx;
@@ -569,6 +570,7 @@ int ssdseg_mask_head_fwd(ssdseg_ctx* ctx, const float* logits, int n, int h, int
 int ssdseg_mask_head_fwd_dice(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx, const float* y_true,
                               const float* class_weights_host, int squared, float* prob, float* loss, float* coef) {
     MASK_HEAD_ARGS();
+    SSDSEG_ARG(n <= 65535, 3);   // the image is gridDim.y of mask_head_fwd_dice_kernel
     SSDSEG_ARG(y_true != nullptr, 9);
     SSDSEG_ARG(class_weights_host != nullptr, 10);
     SSDSEG_ARG(loss != nullptr || coef != nullptr, 13);
@@ -609,6 +611,7 @@ int ssdseg_mask_head_fwd_bootstrap(ssdseg_ctx* ctx, const float* logits, int n, 
                                    const float* class_weights_host, int keep, float* prob, float* pixel_loss, float* thresh, int* kept,
                                    float* loss) {
     MASK_HEAD_ARGS();
+    SSDSEG_ARG(n <= 65535, 3);   // the image is gridDim.y of mask_head_fwd_pixel_kernel and of the select's kernels
     SSDSEG_ARG(y_true != nullptr, 9);
     SSDSEG_ARG(class_weights_host != nullptr, 10);
     const long long npix = (long long)h * fy * wdt * fx;

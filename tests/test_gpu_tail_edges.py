@@ -26,14 +26,13 @@ The bounds are derived, not tuned; the derivations stand with the functions in t
 
 Run with -s for the largest error / bound ratio of every case (DESIGN.md records them).
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import _tail_cases as TC
 from oracle import np_ops as O
 from _guard import BODY_WORD, INPUT_WORD, guards  # noqa: F401  (fixture)
+from _edge_helpers import c4, dev_view, finish, launched, ratio, rejected, reporter, same_bits, untouched
 
 pytestmark = pytest.mark.gpu
 
@@ -41,66 +40,7 @@ F32 = np.float32
 U, ULP = TC.U, TC.ULP
 
 
-def c4(values):
-    return (C.c_float * 4)(*values)
-
-
-def report(kernel, case, **ratios):
-    """prints and asserts the error / bound ratios of one case"""
-    print(f"\ntail-edges {kernel} {case}: " + " ".join(f"{k}={v:.3g}" for k, v in ratios.items()))
-    for k, v in ratios.items():
-        assert v <= 1.0, f"{kernel} {case}: {k} is {v:.3g} x its bound"
-
-
-def ratio(got, ref, bound):
-    """largest |got - ref| / bound; where the bound is 0 the result must be exact"""
-    got, ref, bound = (np.asarray(a, np.float64) for a in (got, ref, bound))
-    bound = np.broadcast_to(bound, got.shape)
-    assert np.isfinite(got).all(), f"{int((~np.isfinite(got)).sum())} elements are not finite"
-    err = np.abs(got - ref)
-    exact = bound == 0
-    assert not err[exact].any(), "an element whose bound is 0 differs"
-    return float((err[~exact] / bound[~exact]).max()) if (~exact).any() else 0.0
-
-
-def finish(ctx, guards):
-    ctx.sync()
-    guards.check()
-
-
-def launched(ctx, fn):
-    """{kernel symbol: launches} of the calls fn() makes"""
-    ctx.timing(True)
-    ctx.timing_reset()
-    try:
-        fn()
-        ctx.join()
-        return {k: r["count"] for k, r in ctx.timing_report().items()}
-    finally:
-        ctx.timing(False)
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a).view(np.uint32), np.asarray(b).view(np.uint32))
-
-
-def untouched(buf):
-    """number of elements of an output body that still hold the poison"""
-    return int((buf.download().view(np.uint32) == np.uint32(BODY_WORD)).sum())
-
-
-def dev_view(guards, x, scale=None, shift=None, act=O.ACT_NONE, ld=None):
-    from ssdseglib import _hip as H
-    xb = guards.inp(x, ld=ld)
-    if scale is None:
-        return H.view(xb, act=act)
-    return H.view(xb, guards.inp(scale), guards.inp(shift), act)
-
-
-def rejected(ctx, name, *args):
-    from ssdseglib import _hip as H
-    with pytest.raises(H.SsdsegError, match=f"{name}: invalid argument"):
-        ctx.call(name, *args)
+report = reporter("tail-edges")
 
 
 # ------------------------------------------------------------------------------------------------------------------ dice
