@@ -617,6 +617,7 @@ int ssdseg_dwconv_bwd(ssdseg_ctx* ctx, const ssdseg_view* in, const float* w, co
                       float* dw, int n, int h, int wdt, int c, int stride, int dilation, int accumulate) {
     SSDSEG_ARG(ctx != nullptr, 1);
     SSDSEG_ARG(in != nullptr && in->x != nullptr, 2);
+    SSDSEG_ARG((in->scale == nullptr) == (in->shift == nullptr), 2);
     SSDSEG_ARG(w != nullptr, 3);
     SSDSEG_ARG(dy != nullptr && dy->g != nullptr, 4);
     SSDSEG_ARG(dy->scale == nullptr || (dy->y && dy->shift && dy->k1 && dy->k0), 4);
@@ -639,6 +640,7 @@ int ssdseg_dwconv_bwd_bn(ssdseg_ctx* ctx, const ssdseg_view* in, const float* w,
     SSDSEG_ARG(dx != nullptr, 5);
     SSDSEG_ARG(dw != nullptr, 6);
     SSDSEG_ARG(n > 0 && h > 0 && wdt > 0, 7);
+    SSDSEG_ARG((long long)n * h * wdt <= 0x7fffffffLL, 7);   // (the unfused reduction counts pixels in an int)
     SSDSEG_ARG(c > 0 && c % 4 == 0, 10);
     SSDSEG_ARG(stride == 1 || stride == 2, 11);
     SSDSEG_ARG(dilation >= 1 && (dilation == 1 || stride == 1), 12);
