@@ -488,6 +488,36 @@ int ssdseg_crop_inputs(ssdseg_ctx* ctx, const uint8_t* src_images, const uint8_t
 int ssdseg_crop_gt(ssdseg_ctx* ctx, const float* src_gt, const int32_t* src_cnt, int n_src, const int32_t* index_host,
                    const float* windows_host, float* gt, int32_t* gt_count, int b, int gmax, int h, int w);
 
+/* Mosaic augmentation on the device (datacoder.random_mosaic; the reference has none: opt-in), in the crop's place in front of the
+ * flip and the colour augmentation; a batch is cropped or assembled, not both.  Output sample n of size H x W is cut by the split
+ * point split_host[n] = (px, py), 0 <= px <= W, 0 <= py <= H, into the quadrants k = 0 top-left [0, px) x [0, py), 1 top-right
+ * [px, W) x [0, py), 2 bottom-left [0, px) x [py, H), 3 bottom-right [px, W) x [py, H); a quadrant of zero width or height is empty
+ * and contributes nothing.  Tile k shows the window windows_host[n][k] = (x0, y0, w, h), in source-pixel units, of source sample
+ * index4_host[n][k], mapped onto quadrant k = (qx, qy, qw, qh).  All three lists are HOST arrays ([b][4] int32, [b][2] int32,
+ * [b][4][4] float32, none may be NULL), validated here -- every index in [0, n_src), every split inside the image, every window,
+ * those of empty quadrants included, finite with 1 <= w <= 16 W, 1 <= h <= 16 H, |x0| <= 16 W, |y0| <= 16 H, else the argument
+ * error and nothing is launched -- and passed to the kernels by value, 16 samples per launch: no copy, no synchronisation, the
+ * caller may overwrite them as soon as the call returns.  All arithmetic is float32 in the order of the host spec
+ * datacoder._mosaic_resample / _mosaic_gt, without FMA contraction; the divisions w / qw, qw / w, ... are done on the host: the
+ * results are the spec's bytes.  The outputs are a dense compact batch, as those of the crop calls, and must not overlap the sources.
+ * ssdseg_mosaic_inputs: output pixel (ox, oy) of quadrant k has the source coordinate u = x0 + ((ox - qx) + 0.5) (w / qw), v
+ *   likewise; the byte is ssdseg_crop_inputs' bilinear value of the four taps around (u, v) in source index4_host[n][k] (a tap
+ *   outside the source IMAGE -- not the window -- is fill_rgb_host[3], NULL: 0, 0, 0), the class index its nearest pixel
+ *   (fill_class, 0..255, outside).  Either source / destination pair may be NULL.  A sample with split (W, H) and tile-0 window
+ *   (0, 0, W, H) is a copy of its source.  flip_host [b] u8 or NULL: the batch's flags, not applied but written to flip_out [b]
+ *   (device, 0 / 1), as ssdseg_crop_inputs does.  Pool offsets are 64-bit; h * w * 3 < 2^31.
+ * ssdseg_mosaic_gt: src_gt [n_src][gmax][5] = (label, xmin, ymin, xmax, ymax), src_cnt [n_src] -> gt [b][gmax][5], gt_count [b].
+ *   Tiles are visited in the order 0..3, empty quadrants skipped, the source's rows in their order.  A row is kept iff its centre
+ *   has x0 <= cx < x0 + w and y0 <= cy < y0 + h and, after x' = qx + (x - x0) (qw / w) clipped to [qx, qx + qw] and y' likewise,
+ *   both extents are >= 1.  Kept rows are concatenated in visiting order; the first gmax are written, gt_count = min(total, gmax),
+ *   rows past the count are zeros.  A tile whose quadrant is the whole image and whose window is exactly (0, 0, W, H) copies its
+ *   source's rows verbatim (no centre test, no clip). */
+int ssdseg_mosaic_inputs(ssdseg_ctx* ctx, const uint8_t* src_images, const uint8_t* src_masks, int n_src, const int32_t* index4_host,
+                         const int32_t* split_host, const float* windows_host, const uint8_t* fill_rgb_host, int fill_class,
+                         const uint8_t* flip_host, uint8_t* flip_out, uint8_t* images_u8, uint8_t* mask_index_u8, int b, int h, int w);
+int ssdseg_mosaic_gt(ssdseg_ctx* ctx, const float* src_gt, const int32_t* src_cnt, int n_src, const int32_t* index4_host,
+                     const int32_t* split_host, const float* windows_host, float* gt, int32_t* gt_count, int b, int gmax, int h, int w);
+
 /* ---------------------------------------------------------------- training metrics
  * Per-image values of the three metric factories NB03#cell14 passes to compile(metrics=...); Keras averages them.
  * jaccard_iou_segmentation_masks_metric (metrics.py:35-47): SOFT Jaccard, inter = sum t*p, total = sum(t+p) over pixels,

@@ -1,10 +1,10 @@
-// How a block of the input-pipeline kernels (inputs.hip, crop.hip) learns which source sample it reads and whether it mirrors it,
+// How a block of the input-pipeline kernels (inputs.hip, crop.hip, mosaic.hip) learns which source sample it reads and whether it mirrors it,
 // and the host code that goes with that.  blockIdx.y is the sample within one launch, n0 the launch's first output sample; a
 // selection `sel` answers for output sample n0 + n with
 //   sel.source(n0, n)     its source sample (64-bit: sample * h * w * 3 passes 2^32 at 4,661 samples of 480x640)
 //   sel.mirrored(n0, n)   its flip flag
-// and says in `chunk` how many samples one launch may cover.  No floating-point arithmetic in here: crop.hip is built with
-// another -ffp-contract than inputs.hip.
+// and says in `chunk` how many samples one launch may cover.  No floating-point arithmetic in here: crop.hip and mosaic.hip are built
+// with another -ffp-contract than inputs.hip (their sampling arithmetic is in crop_sample.h).
 #pragma once
 #include <cmath>
 

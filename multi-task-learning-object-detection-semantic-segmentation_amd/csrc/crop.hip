@@ -11,9 +11,9 @@
 // divisions, w / W and W / w, are done on the host, correctly rounded), so it agrees with it byte for byte
 // (tests/test_gpu_random_crop.py).  The source is a pool + a host index list, or a plain batch (index list NULL: n -> n); indices,
 // windows and fill travel BY VALUE in the kernel arguments beside the gather_sel block of batch_sel.h, 64 samples per launch.
-#include <cmath>
-
+// The sampling arithmetic itself (pixel centre, row setup, bilinear byte, nearest class) is in crop_sample.h, shared with mosaic.hip.
 #include "batch_sel.h"
+#include "crop_sample.h"
 
 namespace {
 
@@ -23,64 +23,6 @@ struct crop_sel {
     float scale[gather_sel::chunk][2];       // crop_inputs: (sx, sy) = (w / W, h / H); crop_gt: (kx, ky) = (W / w, H / h)
     uint32_t fill;                           // r | g << 8 | b << 16 | fill_class << 24
 };
-
-// o + (i + 0.5) * s: the centre of output pixel i in source units
-__device__ __forceinline__ float crop_centre(float o, int i, float s) {
-#pragma clang fp contract(off)
-    return o + ((float)i + 0.5f) * s;
-}
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// the source rows of one output row: bilinear taps yf, yf + 1 (addresses clamped into the image, `in` says whether the row exists)
-// and the nearest row of the mask
-struct crop_rows {
-    int y0, y1, ym;
-    bool in0, in1, inm;
-    float ay;
-};
-
-__device__ __forceinline__ crop_rows crop_row_setup(float wy0, float sy, int oy, int h) {
-#pragma clang fp contract(off)
-    crop_rows r;
-    const float v = crop_centre(wy0, oy, sy);
-    const float Y = v - 0.5f, yf = floorf(Y);
-    r.ay = Y - yf;
-    const int yi = (int)yf, ym = (int)floorf(v);
-    r.in0 = yi >= 0 && yi < h;
-    r.in1 = yi + 1 >= 0 && yi + 1 < h;
-    r.inm = ym >= 0 && ym < h;
-    r.y0 = clampi(yi, h - 1); r.y1 = clampi(yi + 1, h - 1); r.ym = clampi(ym, h - 1);
-    return r;
-}
-
-// one output pixel: 3 bytes from the four taps.  Every address is clamped into the image first; the fill is selected afterwards.
-__device__ __forceinline__ void crop_pixel(const uint8_t* __restrict__ src, const crop_rows& r, float u, int w, const float fill[3], uint32_t out[3]) {
-#pragma clang fp contract(off)
-    const float X = u - 0.5f, xf = floorf(X), ax = X - xf;
-    const int xi = (int)xf;
-    const bool inx0 = xi >= 0 && xi < w, inx1 = xi + 1 >= 0 && xi + 1 < w;
-    const uint8_t* p00 = src + ((long long)r.y0 * w + clampi(xi, w - 1)) * 3;
-    const uint8_t* p01 = src + ((long long)r.y0 * w + clampi(xi + 1, w - 1)) * 3;
-    const uint8_t* p10 = src + ((long long)r.y1 * w + clampi(xi, w - 1)) * 3;
-    const uint8_t* p11 = src + ((long long)r.y1 * w + clampi(xi + 1, w - 1)) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float a00 = (float)p00[c], a01 = (float)p01[c], a10 = (float)p10[c], a11 = (float)p11[c];
-        const float t00 = r.in0 && inx0 ? a00 : fill[c], t01 = r.in0 && inx1 ? a01 : fill[c];
-        const float t10 = r.in1 && inx0 ? a10 : fill[c], t11 = r.in1 && inx1 ? a11 : fill[c];
-        const float top = t00 + (t01 - t00) * ax;
-        const float bot = t10 + (t11 - t10) * ax;
-        const float v = top + (bot - top) * r.ay;
-        out[c] = (uint32_t)floorf(v + 0.5f);             // v lies between its taps: [0, 255]
-    }
-}
-
-__device__ __forceinline__ uint32_t crop_class(const uint8_t* __restrict__ src, const crop_rows& r, float u, int w, uint32_t fill_class) {
-    const int xm = (int)floorf(u);
-    const uint32_t k = src[(long long)r.ym * w + clampi(xm, w - 1)];
-    return r.inm && xm >= 0 && xm < w ? k : fill_class;
-}
 
 // VEC (w % 4 == 0, dword-aligned outputs): four consecutive output pixels of one row per thread, stored as 3 dwords of pixels and
 // 1 dword of class indices.  Otherwise one pixel per thread and byte stores.  blockIdx.y is the sample within the chunk.
@@ -177,18 +119,6 @@ __global__ void __launch_bounds__(64) crop_gt_kernel(const float* __restrict__ s
     if (lane == 0) gt_count[n0 + n] = base;
 }
 
-// every window finite and inside the range that keeps each float -> int conversion of the kernels in range
-bool windows_in_range(const float* win, int b, int h, int w) {
-    const float mw = 16.f * (float)w, mh = 16.f * (float)h;
-    for (int i = 0; i < b; ++i) {
-        const float* q = win + 4 * i;
-        if (!(std::isfinite(q[0]) && std::isfinite(q[1]) && std::isfinite(q[2]) && std::isfinite(q[3]))) return false;
-        if (!(q[2] >= 1.f && q[2] <= mw && q[3] >= 1.f && q[3] <= mh)) return false;
-        if (!(std::fabs(q[0]) <= mw && std::fabs(q[1]) <= mh)) return false;
-    }
-    return true;
-}
-
 // samples [n0, n0 + count) of the host lists as one kernel-argument block; inverse: the scales of crop_gt
 crop_sel make_crop_sel(const int32_t* index_host, const float* win, int n0, int count, int h, int w, bool inverse, uint32_t fill,
                        const uint8_t* flip_host) {
@@ -226,8 +156,7 @@ int ssdseg_crop_inputs(ssdseg_ctx* ctx, const uint8_t* src_images, const uint8_t
     SSDSEG_ARG(indices_in_source(index_host, b, n_src), 5);
     SSDSEG_ARG(windows_in_range(windows_host, b, h, w), 6);
     const int hw = h * w;
-    uint32_t fill = (uint32_t)fill_class << 24;
-    if (fill_rgb_host != nullptr) fill |= (uint32_t)fill_rgb_host[0] | ((uint32_t)fill_rgb_host[1] << 8) | ((uint32_t)fill_rgb_host[2] << 16);
+    const uint32_t fill = pack_fill(fill_rgb_host, fill_class);
     // dword stores: whole groups of 4 pixels per row and dword-aligned outputs (the taps are byte gathers: no condition on the source)
     const bool vec = w % 4 == 0 && (src_images == nullptr || ((uintptr_t)images_u8 & 3) == 0) && (src_masks == nullptr || ((uintptr_t)mask_index_u8 & 3) == 0);
     const int gx = vec ? cdiv(hw, 1024) : cdiv(hw, 256);

@@ -144,6 +144,8 @@ _SIGNATURES = {
     "ssdseg_gather_gt": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _f],
     "ssdseg_crop_inputs": [_vp, _vp, _vp, _i, _vp, C.POINTER(_f), _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i],
     "ssdseg_crop_gt": [_vp, _vp, _vp, _i, _vp, C.POINTER(_f), _vp, _vp, _i, _i, _i, _i],
+    "ssdseg_mosaic_inputs": [_vp, _vp, _vp, _i, _vp, _vp, C.POINTER(_f), _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i],
+    "ssdseg_mosaic_gt": [_vp, _vp, _vp, _i, _vp, _vp, C.POINTER(_f), _vp, _vp, _i, _i, _i, _i],
     "ssdseg_encode_targets": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, C.POINTER(_f), _vp, _vp, _vp],
     "ssdseg_decode_boxes": [_vp, _vp, _vp, _i, _i, C.POINTER(_f), _vp],
     "ssdseg_combined_nms": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp],

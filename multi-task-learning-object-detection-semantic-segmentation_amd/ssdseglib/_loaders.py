@@ -100,9 +100,10 @@ def _encoder_anchors(ctx, encoder, det, mask_op):
 
 
 class _CropStage:
-    """The random-crop step of both loaders (csrc/crop.hip): a batch that carries crop windows is cropped, uint8 -> uint8, into device
-    staging buffers of its own -- pixels, class indices, ground-truth rows, counts: an ordinary compact batch -- and the
-    compact-path calls then run on those.  Crop first, then flip, then colour.  The buffers are allocated on first use."""
+    """The geometric step of both loaders: a batch that carries crop windows (csrc/crop.hip) or a mosaic (csrc/mosaic.hip) is cropped
+    or assembled, uint8 -> uint8, into ONE set of device staging buffers -- pixels, class indices, ground-truth rows, counts: an
+    ordinary compact batch -- and the compact-path calls then run on those.  Crop or mosaic first, then flip, then colour.  The
+    buffers are allocated on first use."""
 
     def __init__(self, ctx, b, h, w, gmax):
         self.ctx, self.b, self.h, self.w, self.gmax = ctx, b, h, w, gmax
@@ -123,6 +124,18 @@ class _CropStage:
         if src_gt is not None:
             self.ctx.call("ssdseg_crop_gt", src_gt, src_cnt, n_src, None if index is None else index.ctypes.data, win, self.gt, self.cnt,
                           self.b, self.gmax, self.h, self.w)
+
+    def run_mosaic(self, src_img, src_midx, src_gt, src_cnt, n_src, mosaic, sources, fill, flip_host):
+        """sources: host int32 (b, 4), the source sample of every tile (a compact batch: mosaic.index4 itself, the positions; a resident
+        batch: the pool slots at those positions); the rest as run()"""
+        fill = fill if fill is not None else (0, 0, 0, 0)
+        sources = np.ascontiguousarray(sources, np.int32)
+        lists = (sources.ctypes.data, mosaic.split.ctypes.data, mosaic.windows.ctypes.data_as(C.POINTER(C.c_float)))
+        self.ctx.call("ssdseg_mosaic_inputs", src_img, src_midx, n_src, *lists, (C.c_uint8 * 3)(*fill[:3]), int(fill[3]),
+                      None if flip_host is None else flip_host.ctypes.data, self.flip, self.img, self.midx if src_midx is not None else None,
+                      self.b, self.h, self.w)
+        if src_gt is not None:
+            self.ctx.call("ssdseg_mosaic_gt", src_gt, src_cnt, n_src, *lists, self.gt, self.cnt, self.b, self.gmax, self.h, self.w)
 
 
 class _EncodingLoader:
@@ -176,7 +189,8 @@ class _CompactLoader(_EncodingLoader):
     uint8 pixels / class indices / ground-truth rows go up on the copy stream (under the running step when fit overlaps);
     consume(): the main stream waits for them and expands them (_expand_compact) straight into the buffers the step reads.  Colour
     draws (datacoder.augmentation_rgb_channels) make ssdseg_rgb_augment produce the image instead of the plain cast (reference
-    datacoder.py:434-466).  Crop windows (datacoder.augmentation_random_crop): cropped first, on the device (_CropStage)."""
+    datacoder.py:434-466).  Crop windows (datacoder.augmentation_random_crop) or a mosaic (datacoder.augmentation_mosaic): cropped
+    or assembled first, on the device (_CropStage)."""
 
     stages_ahead = True
 
@@ -186,7 +200,7 @@ class _CompactLoader(_EncodingLoader):
         self.img = ctx.empty((b, ins.h, ins.w, 3), np.uint8)
         self.midx = ctx.empty((b, ins.h, ins.w), np.uint8)
         self.flip = ctx.empty(b, np.uint8)
-        self.draws = self.windows = self.fill = self._keep = None
+        self.draws = self.windows = self.fill = self.mosaic = self._keep = None
 
     def stage(self, cb, y=None, ahead=False) -> bool:
         b, ins = self.eng.batch, self.eng.input_store
@@ -201,6 +215,9 @@ class _CompactLoader(_EncodingLoader):
         self._keep = [src for _, src in pairs]
         self.draws = getattr(cb, "rgb_draws", None)
         self.windows, self.fill = getattr(cb, "crop_windows", None), getattr(cb, "crop_fill", None)
+        self.mosaic = getattr(cb, "mosaic", None)
+        if self.mosaic is not None:
+            self.fill = getattr(cb, "mosaic_fill", None)
         self.staged = bool(flip.any())
         return True
 
@@ -210,14 +227,17 @@ class _CompactLoader(_EncodingLoader):
         ctx.upload_join()
         flip = self.flip if self.staged else None
         img, midx, gt, cnt = self.img, self.midx, self.gt, self.cnt
-        if self.windows is not None:                # crop first: uint8 -> uint8 into a second compact batch on the device
+        if self.windows is not None or self.mosaic is not None:     # first: uint8 -> uint8 into a second compact batch on the device
             crop = self._crop_stage()
-            crop.run(img, midx if self.mask_op is not None else None, gt if self.det is not None else None, cnt, b, None, self.windows,
-                     self.fill, None)
+            src = (img, midx if self.mask_op is not None else None, gt if self.det is not None else None, cnt, b)
+            if self.mosaic is not None:
+                crop.run_mosaic(*src, self.mosaic, self.mosaic.index4, self.fill, None)
+            else:
+                crop.run(*src, None, self.windows, self.fill, None)
             img, midx, gt, cnt = crop.img, crop.midx, crop.gt, crop.cnt
         self._expand_compact(img, midx, gt, cnt, flip, self.draws)
         ctx.upload_fence()                          # from here on the compact staging buffers may be overwritten
-        self.staged = self.draws = self.windows = self.fill = None
+        self.staged = self.draws = self.windows = self.fill = self.mosaic = None
 
 
 class _ResidentLoader(_EncodingLoader):
@@ -226,7 +246,8 @@ class _ResidentLoader(_EncodingLoader):
     colour augmentation, mirrored where flagged), ssdseg_gather_gt (rows, counts, mirrored boxes), ssdseg_encode_targets -- with
     the bits _CompactLoader gives for `dataset.to_compact(batch)`.  Nothing is uploaded and nothing waits.  Crop windows
     (ResidentDataset(random_crop=...)): cropped from the pools into compact buffers instead (_CropStage takes the index list and
-    hands the flip flags on in its kernel arguments), and the compact-path calls run on those."""
+    hands the flip flags on in its kernel arguments), and the compact-path calls run on those.  A mosaic (ResidentDataset(mosaic=...))
+    likewise: its positions within the batch become pool slots through the batch's index list."""
 
     stages_ahead = False
 
@@ -244,11 +265,15 @@ class _ResidentLoader(_EncodingLoader):
         rb, ctx, b, ins, mask_op = self.staged, self.ctx, self.eng.batch, self.eng.input_store, self.mask_op
         ds = rb.dataset
         self.staged = None
-        if getattr(rb, "crop_windows", None) is not None:
+        mosaic = getattr(rb, "mosaic", None)
+        if getattr(rb, "crop_windows", None) is not None or mosaic is not None:
             crop = self._crop_stage()
             flip_host = rb.flip if rb.flip is not None and rb.flip.any() else None
-            crop.run(ds.images, ds.masks if mask_op is not None else None, ds.gt if self.det is not None else None, ds.cnt, ds.num_samples,
-                     rb.index, rb.crop_windows, rb.crop_fill, flip_host)
+            src = (ds.images, ds.masks if mask_op is not None else None, ds.gt if self.det is not None else None, ds.cnt, ds.num_samples)
+            if mosaic is not None:
+                crop.run_mosaic(*src, mosaic, rb.index[mosaic.index4], rb.mosaic_fill, flip_host)
+            else:
+                crop.run(*src, rb.index, rb.crop_windows, rb.crop_fill, flip_host)
             self._expand_compact(crop.img, crop.midx, crop.gt, crop.cnt, crop.flip if flip_host is not None else None, rb.rgb_draws)
             return
         index = rb.index.ctypes.data

@@ -114,7 +114,7 @@ def _nms_layer(model_inference):
 
 
 def _check_plain(batch) -> None:
-    """evaluation is on the files as they are: no mirrored sample, no colour draws, no crop windows"""
+    """evaluation is on the files as they are: no mirrored sample, no colour draws, no crop windows, no mosaic"""
     kind = type(batch).__name__
     if kind not in ("CompactBatch", "ResidentBatch"):
         raise ValueError(f"evaluate_on_device takes CompactBatch / ResidentBatch objects or a ResidentDataset, got {kind}")
@@ -122,6 +122,8 @@ def _check_plain(batch) -> None:
         raise ValueError("evaluate_on_device: the batch carries colour-augmentation draws")
     if getattr(batch, "crop_windows", None) is not None:
         raise ValueError("evaluate_on_device: the batch carries crop windows; a test set is not augmented")
+    if getattr(batch, "mosaic", None) is not None:
+        raise ValueError("evaluate_on_device: the batch carries a mosaic; a test set is not augmented")
     if batch.flip is not None and np.any(batch.flip):
         raise ValueError("evaluate_on_device: the batch has mirrored samples (flip flags set)")
 
