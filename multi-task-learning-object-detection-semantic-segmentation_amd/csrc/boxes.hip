@@ -232,10 +232,7 @@ __global__ void seg_apply_kernel(const float* __restrict__ probs, const int* __r
     }
 }
 
-int ew_blocks(long long total) {
-    long long b = (total + 255) / 256;
-    return (int)(b < 4096 ? (b < 1 ? 1 : b) : 4096);
-}
+constexpr int BOX_EW_CAP = 4096;   // blocks of the element-wise kernels of this unit (ew_blocks)
 
 }  // namespace
 
@@ -270,7 +267,7 @@ int ssdseg_decode_boxes(ssdseg_ctx* ctx, const float* offsets, const float* anch
     SSDSEG_ARG(stds4_host != nullptr, 6);
     SSDSEG_ARG(corners != nullptr, 7);
     const long long total = (long long)b * a;
-    SSDSEG_LAUNCH(ctx, 32.0 * total, 0.0, decode_kernel, dim3(ew_blocks(total)), dim3(256), 0, offsets, anchors_centroids, total, a,
+    SSDSEG_LAUNCH(ctx, 32.0 * total, 0.0, decode_kernel, dim3(ew_blocks(total, BOX_EW_CAP)), dim3(256), 0, offsets, anchors_centroids, total, a,
                   make_float4(stds4_host[0], stds4_host[1], stds4_host[2], stds4_host[3]), corners);
     SSDSEG_LAUNCH_CHECK();
     return 0;
@@ -312,10 +309,10 @@ int ssdseg_seg_suppress(ssdseg_ctx* ctx, const float* mask_prob, int n_pixels_to
     int rc = ssdseg_workspace(ctx, 16, &ws);
     if (rc) return rc;
     SSDSEG_HIP(hipMemsetAsync(ws, 0, 16, ctx->stream));
-    SSDSEG_LAUNCH(ctx, 16.0 * n_pixels_total, 0.0, seg_present_kernel, dim3(ew_blocks(n_pixels_total)), dim3(256), 0, mask_prob,
+    SSDSEG_LAUNCH(ctx, 16.0 * n_pixels_total, 0.0, seg_present_kernel, dim3(ew_blocks(n_pixels_total, BOX_EW_CAP)), dim3(256), 0, mask_prob,
                   (long long)n_pixels_total, (int*)ws);
     SSDSEG_LAUNCH_CHECK();
-    SSDSEG_LAUNCH(ctx, 32.0 * rows, 0.0, seg_apply_kernel, dim3(ew_blocks(rows)), dim3(256), 0, probs, (const int*)ws, (long long)rows, probs_out);
+    SSDSEG_LAUNCH(ctx, 32.0 * rows, 0.0, seg_apply_kernel, dim3(ew_blocks(rows, BOX_EW_CAP)), dim3(256), 0, probs, (const int*)ws, (long long)rows, probs_out);
     SSDSEG_LAUNCH_CHECK();
     return 0;
 }

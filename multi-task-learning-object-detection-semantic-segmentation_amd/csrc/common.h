@@ -41,7 +41,7 @@ struct ssdseg_ctx {
     // RCCL communicator of this rank (comm.hip; ncclComm_t behind a void* so that only comm.hip needs the RCCL header)
     void* comm;
     int comm_rank, comm_world;
-    // deferred column sums of weight-gradient partial slabs (bn.hip: ssdseg_colsum_defer / ssdseg_colsum_flush)
+    // deferred column sums of weight-gradient partial slabs (colsum.hip: ssdseg_colsum_defer / ssdseg_colsum_flush)
     struct ssdseg_defer* defer;
     // debug poison (ssdseg_ctx_debug_poison, off by default): fresh allocations and every workspace / arena handout start as
     // SSDSEG_POISON_WORD, so a kernel that leaves part of its output or of its partial table unwritten shows NaN instead of the
@@ -88,12 +88,12 @@ int ssdseg_hip_fail(hipError_t e, const char* what);
 // workspace of at least `bytes` (grows with hipMalloc)
 int ssdseg_workspace(ssdseg_ctx* ctx, size_t bytes, void** out);
 // storage for the partial slabs / rows a later ssdseg_colsum reads: the stream's workspace, or -- while column sums are deferred
-// (ssdseg_colsum_defer) -- a persistent arena whose regions live until the flush (bn.hip)
+// (ssdseg_colsum_defer) -- a persistent arena whose regions live until the flush (colsum.hip)
 int ssdseg_partials(ssdseg_ctx* ctx, size_t bytes, void** out);
 // bn.hip: (dgamma, dbeta, k1, k0) from nparts partial rows of (sum mask*g, sum mask*g*xhat)
 int ssdseg_bn_bwd_finalize_launch(ssdseg_ctx* ctx, const float* part, int nparts, int c, double count, const float* scale,
                                   const float* mean, const float* invstd, float* dgamma, float* dbeta, float* k1, float* k0);
-// bn.hip: out[i] = sum over the nparts rows of part[.][len], fixed order
+// colsum.hip: out[i] = sum over the nparts rows of part[.][len], fixed order
 int ssdseg_colsum(ssdseg_ctx* ctx, const float* part, int nparts, long long len, float* out);
 // launches the pending column sums of a deferred backward pass as ONE kernel on the ctx stream (called by ssdseg_join once the
 // side stream has been joined); no-op when nothing is pending
@@ -125,6 +125,12 @@ void ssdseg_defer_hold(ssdseg_ctx* ctx, int delta);
     } while (0)
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// grid of an element-wise, grid-stride kernel of 256-thread blocks: a thread per element, at most `cap` blocks
+static inline int ew_blocks(long long total, int cap = 8192) {
+    long long b = (total + 255) / 256;
+    return (int)(b < cap ? (b < 1 ? 1 : b) : cap);
+}
 
 // Environment switches.  Read on every call, never cached: the parity tests flip them inside one process.
 // env_set: the variable is set, to whatever;  env_is: it is set and starts with `ch`;  env_int: its integer value, `fallback` when unset;

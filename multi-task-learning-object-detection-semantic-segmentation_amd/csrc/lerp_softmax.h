@@ -1,16 +1,10 @@
 // What resize.hip, mask_head.hip and heads.hip share: the half-pixel bilinear geometry (source rows / columns of an output, the
-// four-corner blend, the output window of an input pixel), the 4-class softmax, the 256-thread block sum, and two host helpers.
+// four-corner blend, the output window of an input pixel), the 4-class softmax, the 256-thread block sum, and a host helper.
 // Each expression is written here once: the kernels that claim bit-identity with one another (x4 / general resize, tile / gather
 // mask-head backward) get it from the same text.  Units are built with -ffp-contract=fast: keep the written form of every
 // product and sum.
 #pragma once
 #include "common.h"
-
-// grid of an element-wise, grid-stride kernel
-static inline int ew_blocks(long long total, int threads = 256) {
-    long long b = (total + threads - 1) / threads;
-    return (int)(b < 8192 ? (b < 1 ? 1 : b) : 8192);
-}
 
 // four host floats (class weights, box standard deviations) as a kernel argument
 static inline float4 f4_of(const float* v) { return make_float4(v[0], v[1], v[2], v[3]); }

@@ -6,11 +6,6 @@
 
 namespace {
 
-int ew_blocks(long long total) {
-    long long b = (total + 255) / 256;
-    return (int)(b < 8192 ? (b < 1 ? 1 : b) : 8192);
-}
-
 struct PoolGeom {
     int n, h, w, cv, ho, wo, pt, pl;
 };

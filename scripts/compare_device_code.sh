@@ -17,9 +17,9 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 TMP=${KEEP:-$(mktemp -d)}
 [ -n "$KEEP" ] || trap 'rm -rf "$TMP"' EXIT
 
-compile_one() {   # unit.hip out_dir  (run inside the csrc directory; boxes.hip is built without FMA contraction, as in the Makefile)
+compile_one() {   # unit.hip out_dir  (run inside the csrc directory; the units whose Makefile line sets -ffp-contract=off are built without FMA contraction)
     local contract=fast
-    [ "$1" = boxes.hip ] && contract=off
+    grep -Eq "^${1%.hip}\.o:[[:space:]]*CXXFLAGS[[:space:]]*:=.*-ffp-contract=off" Makefile 2> /dev/null && contract=off
     $HIPCC -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=$contract -w -I../../include -I. \
         --cuda-device-only --no-gpu-bundle-output -c "$1" -o "$2/${1%.hip}.co"
 }

@@ -29,7 +29,7 @@ MAX_BLOCK_Y = 64        # csrc/bn.hip row_launch: the largest blockDim.y, i.e. t
 
 # ------------------------------------------------------------------------------------------------- mirrors of the host code
 def reduce_rc(nparts, length):
-    """channels per block of the partial-row reductions: mirror of reduce_rc in csrc/bn.hip"""
+    """channels per block of the partial-row reductions: mirror of reduce_rc in csrc/reduce_parts.h"""
     if nparts < 32:
         return 32
     return 2 if (nparts >= 256 and length < 2048) else 8

@@ -585,3 +585,28 @@ def row_terms(k, view, gview):
         only[:, r] = dy[:, r]
         rows.append(O.dwconv_bwd(a, k.w.astype(np.float64), only, s, d)[1])
     return y.sum(axis=(0, 2)), np.array(rows)
+
+
+# ------------------------------------------------------------------------------------- a mixed batch of deferred column sums
+# Four ssdseg_dwconv_bwd calls (stride 1, dilation 1, default switches) whose weight-gradient slab tables take every route of the
+# column-sum dispatch (csrc/colsum.hip): few rows; exactly at the 32-row switch; exactly at the 256-row switch; the wide route.
+# (n, h, w, c): (partial rows of the slab table, channels per block of its column sum)
+COLSUM_MIX = {(1, 8, 12, 8): (8, 32), (2, 128, 128, 8): (32, 8), (2, 256, 256, 16): (256, 2), (1, 8, 8, 512): (8, 32)}
+COLSUM_WIDE = 4096
+
+
+def colsum_rc(nparts, length):
+    """columns per block of a column sum: mirror of colsum_rc in csrc/colsum.hip (without its A/B environment switch)"""
+    import _bn_cases as BC
+    return 32 if length >= COLSUM_WIDE else BC.reduce_rc(nparts, length)
+
+
+def colsum_mix_case(shape):
+    """x, w, two different g on the integer lattice {-3 .. 3} -> (x, w, g, g_other): with an identity view and an identity gradient
+    view every partial and every column sum of dW is an integer of at most 9 n h w < 2^24 (|x g| <= 9 per pixel), exact in float32
+    in any order"""
+    n, h, w, c = shape
+    assert 9 * n * h * w < EXACT
+    rng = seeded(77, *shape)
+    x, g, other = (rng.integers(-3, 4, (n, h, w, c)).astype(F32) for _ in range(3))
+    return x, rng.integers(-3, 4, (3, 3, c)).astype(F32), g, other

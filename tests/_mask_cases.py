@@ -54,7 +54,7 @@ def partial_blocks(npix, cap=256):
 
 
 def ew_blocks(total):
-    """mirror of ew_blocks in csrc/lerp_softmax.h: blocks, and the trips of a thread of the grid-stride loop"""
+    """mirror of ew_blocks in csrc/common.h: blocks, and the trips of a thread of the grid-stride loop"""
     b = max(1, min((total + 255) // 256, EW_CAP))
     return dict(blocks=b, trips=-(-total // (b * 256)))
 

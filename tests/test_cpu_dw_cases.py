@@ -220,6 +220,22 @@ def test_families_of_the_settings():
         assert D.bwd_plan(*shape, D.SETTINGS["march"])["family"] == D.bwd_plan(*shape, {})["family"]
 
 
+def test_colsum_mix_takes_every_route_of_the_column_sum_dispatch():
+    """the four shapes of the mixed deferred batch (tests/test_gpu_bn_edges.py): few rows, exactly at the 32-row switch, exactly at
+    the 256-row switch, the wide route -- three block shapes, four block ranges of different lengths"""
+    import _bn_cases as BC
+    assert [D.bwd_plan(*shape, 1, 1, {})["rows"] for shape in D.COLSUM_MIX] == [8, 32, 256, 8]
+    assert [9 * shape[3] for shape in D.COLSUM_MIX] == [72, 72, 144, 4608]
+    for shape, (rows, rc) in D.COLSUM_MIX.items():
+        assert D.bwd_plan(*shape, 1, 1, {})["rows"] == rows and D.colsum_rc(rows, 9 * shape[3]) == rc, shape
+    assert [rc for _, rc in D.COLSUM_MIX.values()] == [32, 8, 2, 32]
+    # each value sits on its switch: one row fewer, or one column fewer than the wide route, gives another block shape
+    assert D.colsum_rc(31, 72) == 32 and D.colsum_rc(255, 144) == 8 and D.colsum_rc(256, 2048) == 8
+    assert D.colsum_rc(8, 4608) == D.colsum_rc(256, 4608) == 32 and D.colsum_rc(256, 4095) == BC.reduce_rc(256, 4095) == 8
+    blocks = [D.cdiv(9 * shape[3], rc) for shape, (_, rc) in D.COLSUM_MIX.items()]
+    assert blocks == [3, 9, 72, 144]
+
+
 def test_forms_cover_the_views():
     fwd_views = {v for v, _ in D.FWD_FORMS}
     assert fwd_views == {"plain"} | set(D.ACTS) and {s for _, s in D.FWD_FORMS} == {True, False}

@@ -2,9 +2,11 @@
 
 ssdseg_bn_finalize, ssdseg_channel_stats, ssdseg_bn_apply, ssdseg_bn_bwd_reduce, ssdseg_gview_materialize, ssdseg_axpby
 (csrc/bn.hip) and ssdseg_act_bwd (csrc/shuffle.hip) on the cases of tests/_bn_cases.py: row pitches with a gap, every activation
-code, every reduce_parts template on both sides of its switch points, count == 1, clamped variances, the block shapes of
-row_launch.  tests/test_cpu_bn_cases.py vets the references and the cases.  Every buffer is guarded (tests/_guard.py): a gap
-column read yields a NaN, a gap column written is reported, an element left unwritten stays a NaN.
+code, every reduce_parts template (csrc/reduce_parts.h) on both sides of its switch points, count == 1, clamped variances, the
+block shapes of row_launch.  tests/test_cpu_bn_cases.py vets the references and the cases.  Every buffer is guarded
+(tests/_guard.py): a gap column read yields a NaN, a gap column written is reported, an element left unwritten stays a NaN.
+The last test runs the same reduction as column sums (csrc/colsum.hip): a mixed batch of deferred tables against the same
+tables folded one launch each.
 
 The bounds are derived, not tuned.  U = 2^-24 is the float32 unit roundoff, ULP = 2^-23 one ulp relative.
 
@@ -362,4 +364,51 @@ def test_axpby_in_place(ctx, guards, geom):
     buf = guards.out((m, c), ld=ld).upload(case["y"])
     ctx.call("ssdseg_axpby", buf, ld, buf, ld, m, c, 1.0, 1.0)
     assert np.array_equal(buf.download(), case["y"] + case["y"])
+    finish(ctx, guards)
+
+
+# ------------------------------------------------------------------------------------------------- deferred column sums
+def test_mixed_deferred_batch_routes_every_table_to_its_blocks(ctx, guards, monkeypatch):
+    """Four ssdseg_dwconv_bwd calls whose slab tables take every route of the column-sum dispatch (_dw_cases.COLSUM_MIX: block shapes
+    32, 8, 2, 32 over 3, 9, 72 and 144 blocks), launched one by one and then as ONE colsum_batch_kernel (csrc/colsum.hip): table ->
+    block shape -> block range.  Integer lattice, identity views, no dx: every dW is exact, so the two runs and the float64
+    reference agree bit for bit.  In the deferred run the first call is made twice into the same dW, first with another g, last of
+    all with the right one: the later table wins and its blocks come last."""
+    import os
+    import _dw_cases as D
+    from _edge_helpers import launched
+    from ssdseglib import _hip as H
+    for v in D.DW_VARS + ("SSDSEG_COLSUM_RC",):
+        monkeypatch.delenv(v, raising=False)
+    assert not [v for v in D.MARCH_ENV if v in os.environ]
+    calls, conv = [], {}
+    for shape in D.COLSUM_MIX:
+        n, h, w, c = shape
+        x, wgt, g, other = D.colsum_mix_case(shape)
+        ref, ref_other = (O.dwconv_bwd(x.astype(np.float64), wgt.astype(np.float64), gg.astype(np.float64), 1, 1)[1] for gg in (g, other))
+        assert ref.any() and not np.array_equal(ref, ref_other)
+        symbol = D.bwd_plan(n, h, w, c, 1, 1, {}, has_dx=False)["symbol"]
+        conv[symbol] = conv.get(symbol, 0) + 1
+        calls.append(dict(dims=(n, h, w, c, 1, 1, 0), x=guards.inp(x), w=guards.inp(wgt), g=guards.inp(g), other=guards.inp(other),
+                          dw=guards.out((3, 3, c)), ref=ref))
+
+    def run(k, g):
+        ctx.call("ssdseg_dwconv_bwd", H.view(k["x"]), k["w"], H.gview(k[g]), None, k["dw"], *k["dims"])
+
+    kernels = launched(ctx, lambda: [run(k, "g") for k in calls])
+    assert kernels == dict(conv, colsum_kernel=4), kernels
+    immediate = [k["dw"].download() for k in calls]
+    for k in calls:
+        guards.repoison(k["dw"])
+    conv[D.bwd_plan(*calls[0]["dims"][:6], {}, has_dx=False)["symbol"]] += 1
+    try:
+        ctx.colsum_defer(True)
+        kernels = launched(ctx, lambda: [run(calls[0], "other")] + [run(k, "g") for k in calls[1:]] + [run(calls[0], "g")])
+    finally:
+        ctx.colsum_defer(False)
+    assert kernels == dict(conv, colsum_batch_kernel=1), kernels
+    for k, first in zip(calls, immediate):
+        got = k["dw"].download()
+        assert np.array_equal(got, first), k["dims"]
+        assert np.array_equal(got, k["ref"]) and np.array_equal(first, k["ref"]), k["dims"]
     finish(ctx, guards)
