@@ -405,6 +405,28 @@ int ssdseg_det_loss_scaled(ssdseg_ctx* ctx, const float* y_labels, const float* 
 int ssdseg_det_loss_focal(ssdseg_ctx* ctx, const float* y_labels, const float* p_labels, const float* y_boxes,
                           const float* p_boxes, int b, int a, int c, const float* alpha4_host, float gamma, float conf_scale,
                           float loc_scale, float* conf_loss, float* loc_loss, float* d_logits, float* d_boxes);
+/* IoU-family box regression loss (not in the reference), forward and gradient: the DETR-style sum
+ *   loss[n] = sum_i box_i (smooth_l1_weight * sl1_i + term_i) / max(sum_i box_i, 1)
+ * over the anchors i of image n.  box_i = 1 if |t.x| + |t.y| + |t.z| + |t.w| > 0 for the target offsets t (localization_loss's
+ * test), sl1_i is localization_loss's smooth-L1 of t - p, and term_i compares the DECODED target box g and predicted box p.
+ * Both offsets o decode alike against the default box (ax, ay, aw, ah) = anchors_centroids[i] (device, [a][4]) and the stds s:
+ *   cx = o.x s.x aw + ax, cy = o.y s.y ah + ay, w = max((exp(o.z s.z) - 1) aw, 0), h = max((exp(o.w s.w) - 1) ah, 0),
+ *   corners cx -+ w/2, cy -+ h/2: continuous boxes, without the +1 / (w - 1)/2 pixel conventions of ssdseg_metric_box_iou and
+ *   ssdseg_decode_boxes.
+ *   iw = max(min(px1, gx1) - max(px0, gx0), 0), ih likewise, I = iw ih, U = pw ph + gw gh - I, IoU = I / (U + 1e-7),
+ *   ew = max(px1, gx1) - min(px0, gx0), eh likewise
+ *   kind 0 (IoU):  term = 1 - IoU
+ *   kind 1 (GIoU): term = 1 - IoU + (E - U) / (E + 1e-7), E = ew eh
+ *   kind 2 (DIoU): term = 1 - IoU + ((pcx - gcx)^2 + (pcy - gcy)^2) / (ew^2 + eh^2 + 1e-7)
+ * d_boxes = loc_scale * d loss[n] / d p through the decode, written for EVERY anchor (exact zeros where box = 0).  At a clamp
+ * (w, h, iw, ih at 0) the derivative is 0; at a tie of a min / max it follows the strict comparison of the spec
+ * (tests/_iou_loss_oracle.py).  An untrained head decodes to boxes of size 0, where the overlap terms alone have a zero gradient
+ * on the size offsets of most anchors: smooth_l1_weight (finite, >= 0; 0 allowed) keeps the smooth-L1 term next to them.
+ * stds4_host: four finite values > 0.  loc_loss [b] and d_boxes [b][a][4] may each be NULL.  Finite inputs only.  Three launches
+ * (per-block partials, per-image fold in fixed order, gradient), no float atomics. */
+int ssdseg_loc_loss_iou(ssdseg_ctx* ctx, const float* y_boxes, const float* p_boxes, const float* anchors_centroids,
+                        const float* stds4_host, int b, int a, int kind, float smooth_l1_weight, float loc_scale,
+                        float* loc_loss, float* d_boxes);
 /* exact top-k selection used by the mining step (tf.math.top_k semantics: larger value first, lower index
  * first among equals, losses.py:131): mask[i] = 1 for the k selected entries of values[n]. */
 int ssdseg_topk_mask(ssdseg_ctx* ctx, const float* values, int n, int k, uint8_t* mask);

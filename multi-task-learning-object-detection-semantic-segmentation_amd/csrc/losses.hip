@@ -7,6 +7,7 @@
 // Integer/selection work is exact: the k-th largest value is found by an MSB-first radix select on order-preserving
 // 32-bit keys and ties are broken by the lower index, which is tf.math.top_k's rule.
 // All float reductions are two-level with a fixed order (no float atomics).
+#include "box_terms.h"
 #include "common.h"
 #include "radix_select.h"
 
@@ -19,27 +20,9 @@ __device__ __forceinline__ float clipf(float p) { return fminf(fmaxf(p, KEPS), 1
 __device__ __forceinline__ float logcr(float p) { return (float)log((double)p); }
 __device__ __forceinline__ float insidef(float p) { return (p >= KEPS && p <= 1.f - KEPS) ? 1.f : 0.f; }
 
-template <int NV>
-__device__ __forceinline__ void block_sum(float (&v)[NV], float* red) {
-    // deterministic tree over 256 threads; result in v[] of thread 0
-    for (int k = 0; k < NV; ++k) {
-        __syncthreads();
-        red[threadIdx.x] = v[k];
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-            __syncthreads();
-        }
-        v[k] = red[0];
-    }
-}
-
 struct AnchorTerms {
     float ce, is_bg, not_bg, sl1, loc_nb;
 };
-
-// 1 for an anchor that carries a box target (localization_loss's own non-background test, losses.py:23-24)
-__device__ __forceinline__ float has_box(float4 yb) { return (fabsf(yb.x) + fabsf(yb.y) + fabsf(yb.z) + fabsf(yb.w)) > 0.f ? 1.f : 0.f; }
 
 // WITH_CE = false leaves t.ce at 0 (the focal loss has its own confidence term and ranks nothing)
 template <bool WITH_CE = true>
@@ -64,18 +47,6 @@ __device__ __forceinline__ AnchorTerms anchor_terms(float4 yl, float4 p, float4 
     }
     t.sl1 = s;
     return t;
-}
-
-// d smooth-L1 / d p_boxes of one anchor, times s (shared by the mined and the focal gradient pass: the same bits)
-__device__ __forceinline__ float4 sl1_grad(float s, float4 ybx, float4 pbx) {
-    const float e[4] = {ybx.x - pbx.x, ybx.y - pbx.y, ybx.z - pbx.z, ybx.w - pbx.w};
-    float d[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float ab = fabsf(e[k]);
-        d[k] = s * (ab < 1.f ? -e[k] : (e[k] > 0.f ? -1.f : (e[k] < 0.f ? 1.f : 0.f)));
-    }
-    return make_float4(d[0], d[1], d[2], d[3]);
 }
 
 // pass 1: per-anchor cross-entropy, background loss vector, per-block partial sums, batch-global counts

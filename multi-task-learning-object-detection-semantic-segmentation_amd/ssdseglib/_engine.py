@@ -793,7 +793,13 @@ class Engine:
                 op.loss = self.ctx.empty(b)
                 op.loss_scale = w / b
                 self._loss_names.append(LossBinding(name, op, "mask", op.y_true, op.loss, op.loss_scale * b))
-            elif fn is LS.confidence_loss or fn is LS.localization_loss or getattr(fn, "loss_kind", None) == "focal":
+            elif fn is LS.confidence_loss or fn is LS.localization_loss or getattr(fn, "loss_kind", None) in ("focal", "iou_loc"):
+                iou_loc = getattr(fn, "loss_kind", None) == "iou_loc"
+                if iou_loc:                         # checked before anything is bound
+                    if not v.meta.get("head_concat") or "logits" in v.meta:
+                        raise ValueError(f"loss {fn.__name__} does not fit output {name}: it takes the box offsets")
+                    if fn.n_anchors != v.store.h * v.store.w:
+                        raise ValueError(f"loss {fn.__name__}: {fn.n_anchors} default boxes, output {name} has {v.store.h * v.store.w} anchors")
                 det = self.loss_ops.get("det")
                 if det is None:
                     labels_v = next(self.vals[id(o)] for o in self.model.outputs if "logits" in self.vals[id(o)].meta)
@@ -805,7 +811,7 @@ class Engine:
                     self.loss_ops["det"] = det
                     self._cur_reach = self.DET_OUTPUTS
                     self._emit(det)
-                if fn is not LS.localization_loss:
+                if fn is not LS.localization_loss and not iou_loc:
                     if fn is not LS.confidence_loss:
                         if "logits" not in v.meta:
                             raise ValueError(f"loss {fn.__name__} does not fit output {name}: it takes the class probabilities")
@@ -815,6 +821,7 @@ class Engine:
                     self._loss_names.append(LossBinding(name, det, "conf", det.y_labels, det.conf_loss, w))
                 else:
                     det.w_loc = w
+                    det.loc, det.loc_kind = (fn, LS.IOU_KINDS[fn.kind]) if iou_loc else (None, 0)
                     self._loss_names.append(LossBinding(name, det, "loc", det.y_boxes, det.loc_loss, w))
             else:
                 raise NotImplementedError(f"loss for output {name}: only the ssdseglib.losses functions are supported")

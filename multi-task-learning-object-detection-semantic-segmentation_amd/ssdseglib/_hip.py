@@ -128,6 +128,7 @@ _SIGNATURES = {
     "ssdseg_det_loss": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
     "ssdseg_det_loss_scaled": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp],
     "ssdseg_det_loss_focal": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _f, _f, _vp, _vp, _vp, _vp],
+    "ssdseg_loc_loss_iou": [_vp, _vp, _vp, _vp, C.POINTER(_f), _i, _i, _i, _f, _f, _vp, _vp],
     "ssdseg_topk_mask": [_vp, _vp, _i, _i, _vp],
     "ssdseg_dice_loss": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), _i, _vp],
     "ssdseg_act_bwd": [_vp, _vp, _i, _vp, _i, _i, _i, _i],

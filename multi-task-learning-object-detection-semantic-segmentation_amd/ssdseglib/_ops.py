@@ -643,7 +643,8 @@ class DetLossOp(Op):
     """confidence (mined or focal) + localization losses; the gradients w.r.t. the pre-softmax logits / box offsets are
     produced in the forward call (fused), each scaled by its own loss weight / batch, and simply stay in the concat stores'
     gradient buffers.  Equal weights with the mined loss take the single-scale entry, the step's bits from before the weights
-    could differ."""
+    could differ.  With losses.iou_localization_loss on the boxes output the localization half is `ssdseg_loc_loss_iou`, called
+    after the confidence entry on the same stream."""
 
     def __init__(self, eng, logits: Store, probs: Store, boxes: Store):
         self.e, self.logits, self.probs, self.boxes = eng, logits, probs, boxes
@@ -654,18 +655,25 @@ class DetLossOp(Op):
         self.w_conf = self.w_loc = 1.0
         self.kind = "mined"                     # "mined": losses.confidence_loss; "focal": losses.focal_confidence_loss(alpha, gamma)
         self.alpha, self.gamma = None, 0.0
+        self.loc, self.loc_kind = None, 0       # None: losses.localization_loss, fused into the confidence entry; else the callable of
+                                                # losses.iou_localization_loss(...) and its kind's number: an entry of its own
 
     def fwd(self):
         p = self.probs
         tr = self.e.training
         ins = (self.y_labels, p.buf, self.y_boxes, self.boxes.buf, p.n, p.h * p.w, p.c)
-        outs = (self.conf_loss, self.loc_loss, self.logits.grad if tr else None, self.boxes.grad if tr else None)
+        iou = self.loc                          # with it the confidence entry runs without its smooth-L1 half: both loc outputs NULL
+        outs = (self.conf_loss, None if iou else self.loc_loss, self.logits.grad if tr else None,
+                self.boxes.grad if tr and not iou else None)
         if self.kind == "focal":
             self.e.ctx.call("ssdseg_det_loss_focal", *ins, self.alpha, self.gamma, self.w_conf / p.n, self.w_loc / p.n, *outs)
-        elif self.w_conf == self.w_loc:
+        elif self.w_conf == self.w_loc or iou:
             self.e.ctx.call("ssdseg_det_loss", *ins, self.w_conf / p.n, *outs, None)
         else:
             self.e.ctx.call("ssdseg_det_loss_scaled", *ins, self.w_conf / p.n, self.w_loc / p.n, *outs, None)
+        if iou:
+            self.e.ctx.call("ssdseg_loc_loss_iou", self.y_boxes, self.boxes.buf, iou.anchors_on(self.e.ctx), iou._stds, p.n, p.h * p.w,
+                            self.loc_kind, iou.smooth_l1_weight, self.w_loc / p.n, self.loc_loss, self.boxes.grad if tr else None)
 
     def bwd(self):
         self.logits.gwritten = True
