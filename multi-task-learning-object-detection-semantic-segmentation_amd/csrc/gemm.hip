@@ -960,7 +960,8 @@ int ssdseg_pwconv_bwd(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, const ssd
 
 // dx = dy * w^T plus the BatchNormalization backward of the layer that feeds this conv (the depthwise BN in front of a project
 // conv): the backward-data kernel's float4 epilogue reduces sum(mask*dx), sum(mask*dx*xhat) while it stores dx.  Only valid when
-// this conv is the ONLY consumer of that BatchNorm's output.  Falls back to the separate reduction pass for unaligned tensors.
+// this conv is the ONLY consumer of that BatchNorm's output.  Falls back to the separate reduction pass for tensors that are not 16-byte
+// aligned (lddx is a multiple of 4: the callers check it).
 // Shared by ssdseg_pwconv_bwd_bn and the tap-expanded form of the narrow 3x3 conv (ssdseg_conv3x3_bwd_data_bn).
 int ssdseg_pwconv_bwd_data_bn(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, const ssdseg_gview* dy, int ldy, const float* w, float* dx,
                               int lddx, int m, int k, int n, const float* in_mean, const float* in_invstd, float* in_dgamma,
@@ -1003,7 +1004,9 @@ int ssdseg_pwconv_bwd_bn(ssdseg_ctx* ctx, const ssdseg_view* in, int ldx, const 
     SSDSEG_ARG(ldy >= n && ldy % 4 == 0, 5);
     SSDSEG_ARG(w != nullptr, 6);
     SSDSEG_ARG(dx != nullptr, 7);
-    SSDSEG_ARG(lddx >= k, 8);
+    // (a multiple of 4: the float4 epilogue stores dx rows as float4 and the fall-back's ssdseg_bn_bwd_reduce reads them back that way;
+    // checked here, before the input-gradient GEMM is launched, not by that reduction after it)
+    SSDSEG_ARG(lddx >= k && lddx % 4 == 0, 8);
     SSDSEG_ARG(dw != nullptr, 9);
     SSDSEG_ARG(m > 0, 10);
     SSDSEG_ARG(k > 0 && k % 4 == 0, 11);
