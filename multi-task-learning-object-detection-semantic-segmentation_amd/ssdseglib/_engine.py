@@ -2,14 +2,13 @@
 for a fixed batch size and mode -- the stand-in for Keras' GradientTape and Adam (third-party).
 Everything stays resident in HBM (288 GB): no recomputation, no activation re-use planning; the launch list is static (no
 Python-side decisions inside a step besides the op order).  The engine owns the parameter bucket, the concat plan, the
-two-stream schedule, the lowering, forward / backward and the loss and metric bindings.  `_loaders` fills its input and target
-buffers; fit / predict / evaluate are `_fit`.
+two-stream schedule, the lowering and forward / backward.  `_loss_bind` binds the compiled losses and metrics to it, `_loaders` fills
+its input and target buffers; fit / predict / evaluate are `_fit`.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
-from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -17,23 +16,10 @@ import numpy as np
 from . import _graph as K
 from . import _hip as H
 from . import layers as L
-from ._ops import (ACT_NONE, ACT_RELU, ActBwdOp, ApplyOp, BilinearOp, BNRec, BnOp, ChannelStatsOp, Conv3Op, DecodeNmsOp, DetLossOp,
-                   DwOp, GapOp, HeadGatherOp, MaskHeadOp, MaxPoolOp, Op, PwOp, ShuffleOp, SoftmaxRowsOp, SplitGatherOp, StemOp, Store,
-                   TableShuffleOp, Val, _act_of, _nonneg, pad4)
-
-
-@dataclass
-class LossBinding:
-    """one compiled loss of one model output, bound to the fused loss op that computes it"""
-    name: str                   # the output's (Keras) name
-    op: Op                      # MaskHeadOp | DetLossOp
-    kind: str                   # "mask" | "conf" | "loc"
-    target: H.DeviceBuffer      # what the step reads as y_true
-    loss: H.DeviceBuffer        # per-sample loss [batch]
-    weight: float               # its share of the total `loss`
-
-    def __iter__(self):         # unpacks as (name, op, kind)
-        return iter((self.name, self.op, self.kind))
+from ._loss_bind import LossBinding, bind_losses, bind_metrics, launch_metrics  # noqa: F401  (LossBinding: re-exported)
+from ._ops import (ACT_NONE, ACT_RELU, ActBwdOp, ApplyOp, BilinearOp, BNRec, BnOp, ChannelStatsOp, Conv3Op, DecodeNmsOp, DwOp, GapOp,
+                   HeadGatherOp, MaskHeadOp, MaxPoolOp, Op, PwOp, ShuffleOp, SoftmaxRowsOp, SplitGatherOp, StemOp, Store, TableShuffleOp,
+                   Val, _act_of, _nonneg, pad4)
 
 
 # ====================================================================================================== engine
@@ -50,7 +36,7 @@ class Engine:
         self.loss_ops: Dict[str, Op] = {}
         self._wt_rows: List[Tuple[int, int, int, int]] = []
         self._wt_table = None
-        self._loss_names, self._metrics = [], []    # configure_losses: LossBinding; configure_metrics: (key, kind, fn, op, buffer)
+        self._loss_names, self._metrics = [], []    # _loss_bind: LossBinding; (key, kind, fn, op, buffer)
         self._plans = None                          # _schedule's (trunk, detection, mask, join_before), dropped by _emit
         self._padded, self._padded_tables = {}, {}  # _padded_view / _sync_padded: zero-padded copies of odd-width weights
         self.loaders: dict = {}                     # _loaders.loader_for: loader class -> what fills this engine's buffers
@@ -760,107 +746,13 @@ class Engine:
 
     # ------------------------------------------------------------------ training step (Keras train_step stand-in)
     def configure_losses(self, loss: dict, loss_weights: dict):
-        """bind the compiled losses to the fused loss ops (reference NB03#cell14: cross_entropy(w) / confidence_loss /
-        localization_loss, weights 1/1/1; Keras reduces each (B,) loss by its batch mean)"""
-        from . import losses as LS
-        self._loss_names = []
-        self.loaders.clear()                        # they hold the bindings' buffers
-        b = self.batch
-        for t in self.model.outputs:
-            name = t.layer.name
-            fn = loss.get(name)
-            if fn is None:
-                continue
-            w = float(loss_weights.get(name, 1.0))
-            v = self.vals[id(t)]
-            if "mask_head" in v.meta:
-                if getattr(fn, "loss_kind", None) not in ("cross_entropy", "dice", "dice_square", "bootstrapped_cross_entropy"):
-                    raise NotImplementedError(f"loss for output {name}: the mask head trains with ssdseglib.losses.cross_entropy / dice / "
-                                              "dice_square / bootstrapped_cross_entropy")
-                op: MaskHeadOp = v.meta["mask_head"]
-                op.kind = fn.loss_kind
-                op.coef = self.ctx.empty((b, 8)) if op.kind in ("dice", "dice_square") else None
-                s = op.logits.store
-                op.keep, op.pixel_loss, op.thresh, op.kept = 0, None, None, None
-                if op.kind == "bootstrapped_cross_entropy":
-                    pixels = s.h * op.fy * s.w * op.fx
-                    op.keep = LS.bootstrap_keep(fn.keep_fraction, pixels)
-                    op.pixel_loss = self.ctx.empty((b, pixels))
-                    op.thresh = self.ctx.empty(b)
-                    op.kept = self.ctx.empty(b, np.int32)
-                op.y_true = self.ctx.empty((b, s.h * op.fy, s.w * op.fx, s.c))
-                op.class_weights = (C.c_float * 4)(*[float(x) for x in fn.classes_weights])
-                op.loss = self.ctx.empty(b)
-                op.loss_scale = w / b
-                self._loss_names.append(LossBinding(name, op, "mask", op.y_true, op.loss, op.loss_scale * b))
-            elif fn is LS.confidence_loss or fn is LS.localization_loss or getattr(fn, "loss_kind", None) in ("focal", "iou_loc"):
-                iou_loc = getattr(fn, "loss_kind", None) == "iou_loc"
-                if iou_loc:                         # checked before anything is bound
-                    if not v.meta.get("head_concat") or "logits" in v.meta:
-                        raise ValueError(f"loss {fn.__name__} does not fit output {name}: it takes the box offsets")
-                    if fn.n_anchors != v.store.h * v.store.w:
-                        raise ValueError(f"loss {fn.__name__}: {fn.n_anchors} default boxes, output {name} has {v.store.h * v.store.w} anchors")
-                det = self.loss_ops.get("det")
-                if det is None:
-                    labels_v = next(self.vals[id(o)] for o in self.model.outputs if "logits" in self.vals[id(o)].meta)
-                    boxes_v = next(self.vals[id(o)] for o in self.model.outputs if self.vals[id(o)].meta.get("head_concat"))
-                    det = DetLossOp(self, labels_v.meta["logits"], labels_v.store, boxes_v.store)
-                    a = labels_v.store.h * labels_v.store.w
-                    det.y_labels = self.ctx.empty((b, a, labels_v.store.c))
-                    det.y_boxes = self.ctx.empty((b, a, 4))
-                    self.loss_ops["det"] = det
-                    self._cur_reach = self.DET_OUTPUTS
-                    self._emit(det)
-                if fn is not LS.localization_loss and not iou_loc:
-                    if fn is not LS.confidence_loss:
-                        if "logits" not in v.meta:
-                            raise ValueError(f"loss {fn.__name__} does not fit output {name}: it takes the class probabilities")
-                        det.kind, det.gamma = "focal", float(fn.gamma)
-                        det.alpha = (C.c_float * 4)(*fn.alpha)
-                    det.w_conf = w
-                    self._loss_names.append(LossBinding(name, det, "conf", det.y_labels, det.conf_loss, w))
-                else:
-                    det.w_loc = w
-                    det.loc, det.loc_kind = (fn, LS.IOU_KINDS[fn.kind]) if iou_loc else (None, 0)
-                    self._loss_names.append(LossBinding(name, det, "loc", det.y_boxes, det.loc_loss, w))
-            else:
-                raise NotImplementedError(f"loss for output {name}: only the ssdseglib.losses functions are supported")
+        bind_losses(self, loss, loss_weights)
 
     def configure_metrics(self, metrics: dict):
-        """bind compile(metrics={output: fn | [fn, ...]}) (NB03#cell14) to the device buffers of this engine's step: the
-        ssdseglib.metrics callables are evaluated by `ssdseg_metric_*` right after the forward pass, from the same target
-        buffers the losses use (needs configure_losses first); Keras naming `<output>_<function name>`"""
-        self._metrics = []
-        targets = {r.name: (r.op, r.kind) for r in self._loss_names}
-        for t in self.model.outputs:
-            name = t.layer.name
-            fns = metrics.get(name)
-            if fns is None:
-                continue
-            for fn in (fns if isinstance(fns, (list, tuple)) else [fns]):
-                kind = getattr(fn, "metric_kind", None)
-                if kind is None:
-                    raise NotImplementedError(f"metric for output {name}: only the ssdseglib.metrics factories are supported")
-                if name not in targets:
-                    raise NotImplementedError(f"metric for output {name} needs a compiled loss on the same output (it shares its target buffer)")
-                op, lkind = targets[name]
-                want = {"mask_iou": "mask", "label_accuracy": "conf", "box_iou": "loc"}[kind]
-                if want != lkind:
-                    raise ValueError(f"metric {fn.__name__} does not fit output {name}")
-                self._metrics.append((f"{name}_{fn.__name__}", kind, fn, op, self.ctx.empty(self.batch)))
+        bind_metrics(self, metrics)
 
     def compute_metrics(self):
-        """launch the metric kernels on the outputs of the forward pass just run (asynchronous; read by `losses()`)"""
-        for key, kind, fn, op, out in self._metrics:
-            if kind == "mask_iou":
-                s = op.logits.store
-                self.ctx.call("ssdseg_metric_mask_iou", s.buf, s.n, s.h, s.w, s.c, op.fy, op.fx, 1, op.y_true, fn._cw, out)
-            elif kind == "label_accuracy":
-                p = op.probs
-                self.ctx.call("ssdseg_metric_label_accuracy", op.y_labels, p.buf, p.n, p.h * p.w, p.c, fn._cw, out)
-            else:
-                p = op.boxes
-                self.ctx.call("ssdseg_metric_box_iou", op.y_boxes, p.buf, fn.anchors_on(self.ctx), fn._stds, p.n, p.h * p.w, out)
+        launch_metrics(self)
 
     def set_targets(self, targets: dict):
         for r in self._loss_names:

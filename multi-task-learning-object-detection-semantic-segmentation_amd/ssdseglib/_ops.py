@@ -563,54 +563,43 @@ class BilinearOp(Op):
 
 
 class MaskHeadOp(Op):
-    """logits --bilinear x(fy,fx)--> softmax (= output-mask) [--> weighted cross-entropy]"""
+    """logits --bilinear x(fy,fx)--> softmax (= output-mask) [--> the bound mask loss, a `_loss_bind` variant]"""
 
     def __init__(self, eng, logits: Val, fy, fx, name, prob: Optional[Store]):
         self.e, self.logits, self.fy, self.fx, self.name, self.prob = eng, logits, fy, fx, name, prob
         s = logits.store
         assert logits.scale is None and logits.act == ACT_NONE and s.ld == s.c
+        self.unbind()
+
+    def unbind(self):
+        """no loss bound: `_loss_bind.bind_losses` sets the variant and what every variant shares"""
+        self.loss_impl = None
         self.y_true: Optional[H.DeviceBuffer] = None
-        self.class_weights: Optional[H.DeviceBuffer] = None
+        self.class_weights = None
         self.loss: Optional[H.DeviceBuffer] = None
         self.loss_scale = 0.0
-        self.kind = "cross_entropy"                       # | "dice" | "dice_square" (reference losses.py:175-307) | "bootstrapped_cross_entropy"
-        self.coef: Optional[H.DeviceBuffer] = None        # dice: per-image backward coefficients left by the forward
-        # bootstrapped cross-entropy: pixels kept per image, and what the forward leaves for the backward -- every pixel's loss
-        # [n][H*W], the per-image threshold [n] -- and the per-image kept count [n]
-        self.keep = 0
-        self.pixel_loss: Optional[H.DeviceBuffer] = None
-        self.thresh: Optional[H.DeviceBuffer] = None
-        self.kept: Optional[H.DeviceBuffer] = None
 
     def fwd(self):
         s = self.logits.store
         prob = self.prob.buf if self.prob is not None else None
-        if self.loss is not None and self.kind == "bootstrapped_cross_entropy":
-            self.e.ctx.call("ssdseg_mask_head_fwd_bootstrap", s.buf, s.n, s.h, s.w, s.c, self.fy, self.fx, self.y_true, self.class_weights,
-                            self.keep, prob, self.pixel_loss, self.thresh, self.kept, self.loss)
-            return
-        if self.loss is not None and self.kind != "cross_entropy":
-            self.e.ctx.call("ssdseg_mask_head_fwd_dice", s.buf, s.n, s.h, s.w, s.c, self.fy, self.fx, self.y_true, self.class_weights,
-                            1 if self.kind == "dice_square" else 0, prob, self.loss, self.coef)
-            return
-        self.e.ctx.call("ssdseg_mask_head_fwd", s.buf, s.n, s.h, s.w, s.c, self.fy, self.fx, self.y_true if self.loss is not None else None,
-                        self.class_weights, prob, self.loss)
+        if self.loss_impl is None:
+            self.e.ctx.call("ssdseg_mask_head_fwd", s.buf, s.n, s.h, s.w, s.c, self.fy, self.fx, None, None, prob, None)
+        else:
+            self.loss_impl.fwd(self, prob)
 
     def bwd(self):
-        if self.loss is None:
+        if self.loss_impl is None:
             return
-        s = self.logits.store
-        g, acc = s.grad_slot()
+        g, acc = self.logits.store.grad_slot()
         assert acc == 0
-        if self.kind == "bootstrapped_cross_entropy":
-            self.e.ctx.call("ssdseg_mask_head_bwd_bootstrap", s.buf, s.n, s.h, s.w, s.c, self.fy, self.fx, self.y_true, self.class_weights,
-                            self.pixel_loss, self.thresh, self.loss_scale, g)
-            return
-        if self.kind != "cross_entropy":
-            self.e.ctx.call("ssdseg_mask_head_bwd_dice", s.buf, s.n, s.h, s.w, s.c, self.fy, self.fx, self.y_true, self.coef,
-                            1 if self.kind == "dice_square" else 0, self.loss_scale, g)
-            return
-        self.e.ctx.call("ssdseg_mask_head_bwd", s.buf, s.n, s.h, s.w, s.c, self.fy, self.fx, self.y_true, self.class_weights, self.loss_scale, g)
+        self.loss_impl.bwd(self, g)
+
+    # read-only views of the bound variant's state (0 / None where it has none), for callers that ask the op
+    kind = property(lambda self: self.loss_impl.kind)
+    keep = property(lambda self: getattr(self.loss_impl, "keep", 0))
+    pixel_loss = property(lambda self: getattr(self.loss_impl, "pixel_loss", None))
+    thresh = property(lambda self: getattr(self.loss_impl, "thresh", None))
+    kept = property(lambda self: getattr(self.loss_impl, "kept", None))
 
 
 class HeadGatherOp(Op):
@@ -640,44 +629,38 @@ class SoftmaxRowsOp(Op):
 
 
 class DetLossOp(Op):
-    """confidence (mined or focal) + localization losses; the gradients w.r.t. the pre-softmax logits / box offsets are
-    produced in the forward call (fused), each scaled by its own loss weight / batch, and simply stay in the concat stores'
-    gradient buffers.  Equal weights with the mined loss take the single-scale entry, the step's bits from before the weights
-    could differ.  With losses.iou_localization_loss on the boxes output the localization half is `ssdseg_loc_loss_iou`, called
-    after the confidence entry on the same stream."""
+    """confidence + localization losses, one `_loss_bind` variant each (`conf_impl`: mined or focal; `loc_impl`: smooth-L1, fused into
+    the confidence entry, or the IoU family, an entry of its own called after it on the same stream).  The gradients w.r.t. the
+    pre-softmax logits / box offsets are produced in the forward call (fused), each scaled by its own loss weight / batch, and simply
+    stay in the concat stores' gradient buffers."""
 
     def __init__(self, eng, logits: Store, probs: Store, boxes: Store):
         self.e, self.logits, self.probs, self.boxes = eng, logits, probs, boxes
         self.name = "det-loss"
-        b = probs.n
-        self.y_labels = self.y_boxes = None
+        b, a = probs.n, probs.h * probs.w
+        self.y_labels, self.y_boxes = eng.ctx.empty((b, a, probs.c)), eng.ctx.empty((b, a, 4))
         self.conf_loss, self.loc_loss = eng.ctx.empty(b), eng.ctx.empty(b)
+        self.conf_impl = self.loc_impl = None   # the two variants and their weights: `_loss_bind.bind_losses`, afresh on every call
         self.w_conf = self.w_loc = 1.0
-        self.kind = "mined"                     # "mined": losses.confidence_loss; "focal": losses.focal_confidence_loss(alpha, gamma)
-        self.alpha, self.gamma = None, 0.0
-        self.loc, self.loc_kind = None, 0       # None: losses.localization_loss, fused into the confidence entry; else the callable of
-                                                # losses.iou_localization_loss(...) and its kind's number: an entry of its own
 
     def fwd(self):
         p = self.probs
         tr = self.e.training
+        fused = self.loc_impl.fused                # else the confidence entry runs without its smooth-L1 half: both loc outputs NULL
         ins = (self.y_labels, p.buf, self.y_boxes, self.boxes.buf, p.n, p.h * p.w, p.c)
-        iou = self.loc                          # with it the confidence entry runs without its smooth-L1 half: both loc outputs NULL
-        outs = (self.conf_loss, None if iou else self.loc_loss, self.logits.grad if tr else None,
-                self.boxes.grad if tr and not iou else None)
-        if self.kind == "focal":
-            self.e.ctx.call("ssdseg_det_loss_focal", *ins, self.alpha, self.gamma, self.w_conf / p.n, self.w_loc / p.n, *outs)
-        elif self.w_conf == self.w_loc or iou:
-            self.e.ctx.call("ssdseg_det_loss", *ins, self.w_conf / p.n, *outs, None)
-        else:
-            self.e.ctx.call("ssdseg_det_loss_scaled", *ins, self.w_conf / p.n, self.w_loc / p.n, *outs, None)
-        if iou:
-            self.e.ctx.call("ssdseg_loc_loss_iou", self.y_boxes, self.boxes.buf, iou.anchors_on(self.e.ctx), iou._stds, p.n, p.h * p.w,
-                            self.loc_kind, iou.smooth_l1_weight, self.w_loc / p.n, self.loc_loss, self.boxes.grad if tr else None)
+        outs = (self.conf_loss, self.loc_loss if fused else None, self.logits.grad if tr else None,
+                self.boxes.grad if tr and fused else None)
+        self.conf_impl.fwd(self, ins, outs)
+        self.loc_impl.fwd(self)
 
     def bwd(self):
         self.logits.gwritten = True
         self.boxes.gwritten = True
+
+    # read-only views of the bound variants: "mined" | "focal"; the losses.iou_localization_loss callable (None: smooth-L1) and its number
+    kind = property(lambda self: self.conf_impl.kind)
+    loc = property(lambda self: self.loc_impl.fn)
+    loc_kind = property(lambda self: self.loc_impl.kind)
 
 
 class DecodeNmsOp(Op):

@@ -1,6 +1,6 @@
 """Training losses with the reference's API (reference losses.py): every function maps (y_true, y_pred) to one loss
 value per batch item, shape (batch,).  Called directly they run the HIP kernels on cuda:0 and return NumPy arrays;
-passed to `model.compile(loss={...})` they select the fused loss ops of the engine (`_engine.configure_losses`),
+passed to `model.compile(loss={...})` they select the fused loss ops of the engine (`_loss_bind.bind_losses`),
 where the gradient comes out of the same launch.
 """
 import ctypes as C
@@ -10,38 +10,67 @@ from typing import Callable, List
 import numpy as np
 
 
+# ---------------------------------------------------------------- what the standalone callables here and in `metrics` share
 def _ctx():
     from . import _engine
     return _engine.default_context()
 
 
-def _f32(a):
-    return np.ascontiguousarray(a, dtype=np.float32)
+def c4(values):
+    """four floats as the host array the C entries take (class weights, alpha, standard deviations)"""
+    return (C.c_float * 4)(*[float(v) for v in values])
 
 
+def shape_of(a):
+    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+
+
+def dev(a):
+    """`a` on the default context: a device buffer as it is, anything else uploaded as float32"""
+    from . import _hip as H
+    return a if isinstance(a, H.DeviceBuffer) else _ctx().array(np.ascontiguousarray(a, dtype=np.float32))
+
+
+OUT = object()      # among `per_sample`'s arguments: the place of the (batch,) result
+
+
+def per_sample(entry: str, batch: int, *args) -> np.ndarray:
+    """call the compiled `entry` on the default context and download the one value per batch item it writes"""
+    ctx = _ctx()
+    out = ctx.empty(batch)
+    ctx.call(entry, *[out if a is OUT else a for a in args])
+    return out.download()
+
+
+def boxes_on_context(anchors: np.ndarray) -> Callable:
+    """-> anchors_on(ctx): the default boxes [a][4] = cx, cy, w, h on `ctx`'s device, uploaded once per context (data-parallel
+    ranks each have one)"""
+    state = {}
+
+    def anchors_on(ctx):
+        if id(ctx) not in state:
+            state[id(ctx)] = (ctx, ctx.array(anchors))
+        return state[id(ctx)][1]
+
+    return anchors_on
+
+
+# -------------------------------------------------------------------------------------------------------------- the losses
 def localization_loss(y_true, y_pred):
     """smooth-L1 over non-background anchors / max(#non-background, 1) (reference losses.py:21-49)."""
-    y_true, y_pred = _f32(y_true), _f32(y_pred)
-    b, a, _ = y_true.shape
-    ctx = _ctx()
+    b, a, _ = shape_of(y_true)
     dummy_labels = np.zeros((b, a, 4), np.float32)
     dummy_labels[..., 0] = 1.0
-    loc = ctx.empty(b)
-    ctx.call("ssdseg_det_loss", ctx.array(dummy_labels), ctx.array(np.full((b, a, 4), 0.25, np.float32)), ctx.array(y_true), ctx.array(y_pred),
-             b, a, 4, 1.0, None, loc, None, None, None)
-    return loc.download()
+    return per_sample("ssdseg_det_loss", b, dev(dummy_labels), dev(np.full((b, a, 4), 0.25, np.float32)), dev(y_true), dev(y_pred),
+                      b, a, 4, 1.0, None, OUT, None, None, None)
 
 
 def confidence_loss(y_true, y_pred):
     """softmax cross-entropy with batch-global 3:1 hard-negative mining (reference losses.py:70-172);
     y_pred are probabilities."""
-    y_true, y_pred = _f32(y_true), _f32(y_pred)
-    b, a, c = y_true.shape
-    ctx = _ctx()
-    zeros = ctx.zeros((b, a, 4))
-    conf = ctx.empty(b)
-    ctx.call("ssdseg_det_loss", ctx.array(y_true), ctx.array(y_pred), zeros, zeros, b, a, c, 1.0, conf, None, None, None, None)
-    return conf.download()
+    b, a, c = shape_of(y_true)
+    zeros = _ctx().zeros((b, a, 4))
+    return per_sample("ssdseg_det_loss", b, dev(y_true), dev(y_pred), zeros, zeros, b, a, c, 1.0, OUT, None, None, None, None)
 
 
 def focal_confidence_loss(alpha=(1.0, 1.0, 1.0, 1.0), gamma: float = 2.0) -> Callable:
@@ -62,14 +91,10 @@ def focal_confidence_loss(alpha=(1.0, 1.0, 1.0, 1.0), gamma: float = 2.0) -> Cal
         raise ValueError(f"gamma must be finite and >= 0, got {gamma}")
 
     def loss_fn(y_true, y_pred):
-        y_true, y_pred = _f32(y_true), _f32(y_pred)
-        b, a, c = y_true.shape
-        ctx = _ctx()
-        zeros = ctx.zeros((b, a, 4))
-        conf = ctx.empty(b)
-        ctx.call("ssdseg_det_loss_focal", ctx.array(y_true), ctx.array(y_pred), zeros, zeros, b, a, c, (C.c_float * 4)(*weights), gamma, 1.0, 1.0,
-                 conf, None, None, None)
-        return conf.download()
+        b, a, c = shape_of(y_true)
+        zeros = _ctx().zeros((b, a, 4))
+        return per_sample("ssdseg_det_loss_focal", b, dev(y_true), dev(y_pred), zeros, zeros, b, a, c, c4(weights), gamma, 1.0, 1.0,
+                          OUT, None, None, None)
 
     loss_fn.__name__ = "focal_confidence_loss"
     loss_fn.alpha = weights
@@ -111,24 +136,14 @@ def iou_localization_loss(center_x_boxes_default, center_y_boxes_default, width_
     if len({v.size for v in defaults}) != 1 or defaults[0].size == 0:
         raise ValueError(f"the default-box vectors must have one common length > 0, got {[v.size for v in defaults]}")
     anchors = np.ascontiguousarray(np.stack(defaults, axis=1))
-    cstds = (C.c_float * 4)(*stds)
-    state = {}
-
-    def anchors_on(ctx):
-        """the default boxes [a][4] = cx, cy, w, h on `ctx`'s device, uploaded once per context (data-parallel ranks each have one)"""
-        if id(ctx) not in state:
-            state[id(ctx)] = (ctx, ctx.array(anchors))
-        return state[id(ctx)][1]
+    cstds, anchors_on = c4(stds), boxes_on_context(anchors)
 
     def loss_fn(y_true, y_pred):
-        y_true, y_pred = _f32(y_true), _f32(y_pred)
-        b, a, _ = y_true.shape
+        b, a, _ = shape_of(y_true)
         if a != anchors.shape[0]:
             raise ValueError(f"{a} boxes per image, {anchors.shape[0]} default boxes")
-        ctx = _ctx()
-        loc = ctx.empty(b)
-        ctx.call("ssdseg_loc_loss_iou", ctx.array(y_true), ctx.array(y_pred), anchors_on(ctx), cstds, b, a, IOU_KINDS[kind], weight, 1.0, loc, None)
-        return loc.download()
+        return per_sample("ssdseg_loc_loss_iou", b, dev(y_true), dev(y_pred), anchors_on(_ctx()), cstds, b, a, IOU_KINDS[kind], weight, 1.0,
+                          OUT, None)
 
     loss_fn.__name__ = "iou_localization_loss"
     loss_fn.loss_kind = "iou_loc"
@@ -141,13 +156,8 @@ def _mask_loss(mode: int, name: str, kind: str, classes_weights: List[float]) ->
     weights = tuple(float(w) for w in classes_weights)
 
     def loss_fn(y_true, y_pred):
-        y_true, y_pred = _f32(y_true), _f32(y_pred)
-        n, c = y_true.shape[0], y_true.shape[-1]
-        hw = int(np.prod(y_true.shape[1:-1]))
-        ctx = _ctx()
-        out = ctx.empty(n)
-        ctx.call("ssdseg_dice_loss", ctx.array(y_true), ctx.array(y_pred), n, hw, c, (C.c_float * 4)(*weights), mode, out)
-        return out.download()
+        n, *hw, c = shape_of(y_true)
+        return per_sample("ssdseg_dice_loss", n, dev(y_true), dev(y_pred), n, int(np.prod(hw)), c, c4(weights), mode, OUT)
 
     loss_fn.__name__ = name
     loss_fn.classes_weights = weights
@@ -182,14 +192,9 @@ def bootstrapped_cross_entropy(classes_weights: List[float], keep_fraction: floa
         raise ValueError(f"keep_fraction must be finite and in (0, 1], got {keep_fraction}")
 
     def loss_fn(y_true, y_pred):
-        y_true, y_pred = _f32(y_true), _f32(y_pred)
-        n, c = y_true.shape[0], y_true.shape[-1]
-        hw = int(np.prod(y_true.shape[1:-1]))
-        ctx = _ctx()
-        out = ctx.empty(n)
-        ctx.call("ssdseg_bootstrap_ce_loss", ctx.array(y_true), ctx.array(y_pred), n, hw, c, (C.c_float * 4)(*weights), bootstrap_keep(keep_fraction, hw),
-                 out)
-        return out.download()
+        n, *hw, c = shape_of(y_true)
+        hw = int(np.prod(hw))
+        return per_sample("ssdseg_bootstrap_ce_loss", n, dev(y_true), dev(y_pred), n, hw, c, c4(weights), bootstrap_keep(keep_fraction, hw), OUT)
 
     loss_fn.__name__ = "bootstrapped_cross_entropy_loss"
     loss_fn.classes_weights = weights
