@@ -595,6 +595,35 @@ int ssdseg_eval_det_best_iou(ssdseg_ctx* ctx, const float* det, const float* gt,
 int ssdseg_adam_step(ssdseg_ctx* ctx, float* params, const float* grads, float* m, float* v, size_t count,
                      float lr, float beta1, float beta2, float eps, int step, float grad_scale);
 
+/* ---------------------------------------------------------------- K20b: SGD and AdamW with a weight-decay run table
+ * Decoupled weight decay as Keras 2.13's optimizers apply it (`weight_decay`): p1 = p - (lr * lambda) * p before the update, with
+ * lr the learning rate itself (for AdamW: not the bias-corrected alpha).  WHERE it applies is a run table over the flat bucket:
+ *   run_end   [nruns] device, ascending exclusive end offsets in elements; run r covers [run_end[r-1], run_end[r]), run 0 from 0
+ *   run_decay [nruns] device, the coefficient lambda of each run
+ * Elements at or beyond the last run_end take lambda = 0, and so does every element when nruns == 0 (both pointers NULL then).
+ * Boundaries are arbitrary (ShuffleNetV2's 58- / 122-channel vectors put them at offsets = 2 mod 4: the four lanes of one
+ * float4 may belong to different runs).  A run with lambda == 0 leaves p1 = p bit for bit.  The table is read through the
+ * caches, a few entries per block (csrc/decay_runs.h): no per-element mask stream.  Whatever the table holds -- ends that do
+ * not ascend, ends beyond `count` -- the kernels touch nothing outside [0, count) of the buffers and nothing outside the
+ * table's nruns entries (the decay then lands where the table's own order says, which is the caller's business).
+ * nruns is at most SSDSEG_DECAY_RUNS_MAX (a 48 KiB table, far beyond the few hundred runs of the models here); more is an
+ * argument error.
+ *
+ * ssdseg_sgd_step -- Keras 2.13 SGD, g' = g * grad_scale:
+ *   momentum == 0:  p = p1 - lr g'                       (velocity may be NULL, it is not touched; 12 B per element)
+ *   momentum  > 0:  v = momentum v - lr g';  p = p1 + v  (20 B per element)
+ *        nesterov:  v likewise;  p = p1 + (momentum v - lr g')
+ *   momentum in [0, 1); nesterov != 0 needs momentum > 0 to mean anything (with momentum == 0 it is ignored).
+ * ssdseg_adamw_step -- ssdseg_adam_step applied to p1: the same kernel body with the decay compiled in; with nruns == 0 it IS
+ *   ssdseg_adam_step's launch, bit for bit. */
+#define SSDSEG_DECAY_RUNS_MAX 4096
+int ssdseg_sgd_step(ssdseg_ctx* ctx, float* params, const float* grads, float* velocity, size_t count, float lr,
+                    float momentum, int nesterov, float grad_scale, const long long* run_end, const float* run_decay,
+                    int nruns);
+int ssdseg_adamw_step(ssdseg_ctx* ctx, float* params, const float* grads, float* m, float* v, size_t count, float lr,
+                      float beta1, float beta2, float eps, int step, float grad_scale, const long long* run_end,
+                      const float* run_decay, int nruns);
+
 /* ---------------------------------------------------------------- K21: ShuffleNetV2-only ops
  * MaxPooling2D 3x3 stride 2 SAME (models.py:629); argmax-free backward (recomputes the window max). */
 int ssdseg_maxpool3x3s2_fwd(ssdseg_ctx* ctx, const ssdseg_view* in, float* out, int n, int h, int wdt, int c);

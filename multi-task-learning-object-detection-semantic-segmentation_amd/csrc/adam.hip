@@ -1,34 +1,79 @@
 // Adam as Keras 2.13 applies it (NB03#cell14: tf.keras.optimizers.Adam(1e-4); semantics SURVEY.md App. B.10):
 //   m += (g - m)(1 - b1);  v += (g^2 - v)(1 - b2);  p -= lr*sqrt(1 - b2^t)/(1 - b1^t) * m / (sqrt(v) + eps)
 // One fused multi-tensor pass over the flat parameter bucket (HBM-bound: 4 streams read, 3 written).
+// AdamW (ssdseg_adamw_step) is the same body with the decoupled decay p -= (lr lambda) p compiled in front of it; lambda comes
+// from the run table (decay_runs.h), which also makes a block's float4s one contiguous chunk instead of a grid-stride comb.
 #include <math.h>
 
 #include "common.h"
+#include "decay_runs.h"
 
 namespace {
+template <bool DECAY>
+__device__ __forceinline__ void adam_element(float& p, float g, float& m, float& v, float alpha, float one_minus_b1, float one_minus_b2,
+                                             float eps, float gscale, float lr, float lam) {
+    const float gk = g * gscale;
+    if (DECAY) p = decay_apply(p, lr, lam);
+    m += (gk - m) * one_minus_b1;
+    v += (gk * gk - v) * one_minus_b2;
+    p -= alpha * m / (sqrtf(v) + eps);
+}
+
+template <bool DECAY>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n4,
-                            size_t n, float alpha, float one_minus_b1, float one_minus_b2, float eps, float gscale) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float4 pp = ld4(p + 4 * i), gg = ld4(g + 4 * i), mm = ld4(m + 4 * i), vv = ld4(v + 4 * i);
-        float* pe = &pp.x; float* ge = &gg.x; float* me = &mm.x; float* ve = &vv.x;
+                            size_t n, float alpha, float one_minus_b1, float one_minus_b2, float eps, float gscale, float lr, DecayRuns runs) {
+    if (!DECAY) {
+        const size_t stride = (size_t)gridDim.x * blockDim.x;
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+            float4 pp = ld4(p + 4 * i), gg = ld4(g + 4 * i), mm = ld4(m + 4 * i), vv = ld4(v + 4 * i);
+            float* pe = &pp.x; float* ge = &gg.x; float* me = &mm.x; float* ve = &vv.x;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float gk = ge[k] * gscale;
-            me[k] += (gk - me[k]) * one_minus_b1;
-            ve[k] += (gk * gk - ve[k]) * one_minus_b2;
-            pe[k] -= alpha * me[k] / (sqrtf(ve[k]) + eps);
+            for (int k = 0; k < 4; ++k) adam_element<false>(pe[k], ge[k], me[k], ve[k], alpha, one_minus_b1, one_minus_b2, eps, gscale, lr, 0.f);
+            st4(p + 4 * i, pp); st4(m + 4 * i, mm); st4(v + 4 * i, vv);
         }
-        st4(p + 4 * i, pp); st4(m + 4 * i, mm); st4(v + 4 * i, vv);
+    } else {
+        size_t first, last;
+        decay_chunk(n4, &first, &last);
+        size_t i = first + threadIdx.x;
+        float4 pp = f4(0.f), gg = f4(0.f), mm = f4(0.f), vv = f4(0.f);
+        // the first float4s are requested BEFORE the seek: its dependent scalar loads then run under loads the block waits for anyway
+        if (i < last) { pp = ld4(p + 4 * i); gg = ld4(g + 4 * i); mm = ld4(m + 4 * i); vv = ld4(v + 4 * i); }
+        DecayCursor cur = decay_seek(runs, (long long)(first << 2));
+        while (i < last) {
+            float* pe = &pp.x; float* ge = &gg.x; float* me = &mm.x; float* ve = &vv.x;
+            float lam[4];
+            decay_lambda4(runs, cur, (long long)(i << 2), lam);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) adam_element<true>(pe[k], ge[k], me[k], ve[k], alpha, one_minus_b1, one_minus_b2, eps, gscale, lr, lam[k]);
+            st4(p + 4 * i, pp); st4(m + 4 * i, mm); st4(v + 4 * i, vv);
+            i += blockDim.x;
+            if (i < last) { pp = ld4(p + 4 * i); gg = ld4(g + 4 * i); mm = ld4(m + 4 * i); vv = ld4(v + 4 * i); }
+        }
     }
     // tail (n not a multiple of 4)
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const size_t i = (n4 << 2) + threadIdx.x;
-        const float gk = g[i] * gscale;
-        m[i] += (gk - m[i]) * one_minus_b1;
-        v[i] += (gk * gk - v[i]) * one_minus_b2;
-        p[i] -= alpha * m[i] / (sqrtf(v[i]) + eps);
+        const float lam = DECAY ? decay_seek(runs, (long long)i).lam : 0.f;
+        float pi = p[i], mi = m[i], vi = v[i];
+        adam_element<DECAY>(pi, g[i], mi, vi, alpha, one_minus_b1, one_minus_b2, eps, gscale, lr, lam);
+        p[i] = pi; m[i] = mi; v[i] = vi;
     }
+}
+
+int adam_launch(ssdseg_ctx* ctx, float* params, const float* grads, float* m, float* v, size_t count, float lr, float beta1, float beta2,
+                float eps, int step, float grad_scale, const long long* run_end, const float* run_decay, int nruns) {
+    { int jrc = ssdseg_join(ctx); if (jrc) return jrc; }   // weight gradients may still be in flight on the side stream
+    const double alpha = (double)lr * sqrt(1.0 - pow((double)beta2, step)) / (1.0 - pow((double)beta1, step));
+    const size_t n4 = count / 4;
+    const DecayRuns runs = {run_end, run_decay, nruns};
+    if (nruns == 0)
+        SSDSEG_LAUNCH_NAMED(ctx, "adam_kernel", 28.0 * (double)count, 0.0, adam_kernel<false>, dim3(optimizer_blocks(n4)), dim3(256), 0, params,
+                            grads, m, v, n4, count, (float)alpha, 1.f - beta1, 1.f - beta2, eps, grad_scale, lr, runs);
+    else
+        SSDSEG_LAUNCH_NAMED(ctx, "adamw_kernel", 28.0 * (double)count + 12.0 * nruns, 0.0, adam_kernel<true>, dim3(decay_blocks(n4)), dim3(256), 0,
+                            params, grads, m, v, n4, count, (float)alpha, 1.f - beta1, 1.f - beta2, eps, grad_scale, lr, runs);
+    SSDSEG_LAUNCH_CHECK();
+    return 0;
 }
 }  // namespace
 
@@ -38,14 +83,16 @@ extern "C" int ssdseg_adam_step(ssdseg_ctx* ctx, float* params, const float* gra
     SSDSEG_ARG(params && grads && m && v, 2);
     SSDSEG_ARG(step >= 1, 11);
     if (count == 0) return 0;
-    { int jrc = ssdseg_join(ctx); if (jrc) return jrc; }   // weight gradients may still be in flight on the side stream
-    const double alpha = (double)lr * sqrt(1.0 - pow((double)beta2, step)) / (1.0 - pow((double)beta1, step));
-    const size_t n4 = count / 4;
-    size_t blocks = (n4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    SSDSEG_LAUNCH(ctx, 28.0 * (double)count, 0.0, adam_kernel, dim3((unsigned)blocks), dim3(256), 0, params, grads, m, v, n4, count, (float)alpha,
-                       1.f - beta1, 1.f - beta2, eps, grad_scale);
-    SSDSEG_LAUNCH_CHECK();
-    return 0;
+    return adam_launch(ctx, params, grads, m, v, count, lr, beta1, beta2, eps, step, grad_scale, nullptr, nullptr, 0);
+}
+
+extern "C" int ssdseg_adamw_step(ssdseg_ctx* ctx, float* params, const float* grads, float* m, float* v, size_t count, float lr,
+                                 float beta1, float beta2, float eps, int step, float grad_scale, const long long* run_end,
+                                 const float* run_decay, int nruns) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    SSDSEG_ARG(params && grads && m && v, 2);
+    SSDSEG_ARG(step >= 1, 11);
+    SSDSEG_DECAY_ARGS(run_end, run_decay, nruns, 13, 14, 15);
+    if (count == 0) return 0;
+    return adam_launch(ctx, params, grads, m, v, count, lr, beta1, beta2, eps, step, grad_scale, run_end, run_decay, nruns);
 }

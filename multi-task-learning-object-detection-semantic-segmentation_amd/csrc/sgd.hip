@@ -1,0 +1,84 @@
+// SGD as Keras 2.13 applies it (tf.keras.optimizers.SGD with its decoupled `weight_decay`), g' = g * grad_scale:
+//   p1 = p - (lr lambda) p                                   lambda from the run table (decay_runs.h)
+//   momentum == 0:  p = p1 - lr g'                           12 B per element, the velocity is not touched
+//   momentum  > 0:  v = momentum v - lr g';  p = p1 + v      20 B per element
+//        nesterov:  v likewise;  p = p1 + (momentum v - lr g')
+// The recipe of the SSD and DeepLabV3+ papers (momentum 0.9, L2 decay on the convolution kernels, stepped / poly rate).
+// One fused pass over the flat parameter bucket, as csrc/adam.hip: float4 body, scalar tail, a block per contiguous chunk.
+#include "common.h"
+#include "decay_runs.h"
+
+namespace {
+enum { SGD_PLAIN = 0, SGD_MOMENTUM = 1, SGD_NESTEROV = 2 };
+
+template <int MODE>
+__device__ __forceinline__ void sgd_element(float& p, float g, float& v, float lr, float mu, float gscale, float lam) {
+    const float gk = g * gscale;
+    const float p1 = decay_apply(p, lr, lam);
+    if (MODE == SGD_PLAIN) {
+        p = p1 - lr * gk;
+    } else {
+        v = mu * v - lr * gk;
+        p = MODE == SGD_NESTEROV ? p1 + (mu * v - lr * gk) : p1 + v;
+    }
+}
+
+template <int MODE>
+__global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v, size_t n4, size_t n, float lr, float mu,
+                           float gscale, DecayRuns runs) {
+    size_t first, last;
+    decay_chunk(n4, &first, &last);
+    size_t i = first + threadIdx.x;
+    float4 pp = f4(0.f), gg = f4(0.f), vv = f4(0.f);
+    // the first float4s are requested BEFORE the seek: its dependent scalar loads then run under loads the block waits for anyway
+    if (i < last) { pp = ld4(p + 4 * i); gg = ld4(g + 4 * i); if (MODE != SGD_PLAIN) vv = ld4(v + 4 * i); }
+    DecayCursor cur = decay_seek(runs, (long long)(first << 2));
+    while (i < last) {
+        float* pe = &pp.x; float* ge = &gg.x; float* ve = &vv.x;
+        float lam[4];
+        decay_lambda4(runs, cur, (long long)(i << 2), lam);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sgd_element<MODE>(pe[k], ge[k], ve[k], lr, mu, gscale, lam[k]);
+        st4(p + 4 * i, pp);
+        if (MODE != SGD_PLAIN) st4(v + 4 * i, vv);
+        i += blockDim.x;
+        if (i < last) { pp = ld4(p + 4 * i); gg = ld4(g + 4 * i); if (MODE != SGD_PLAIN) vv = ld4(v + 4 * i); }
+    }
+    // tail (n not a multiple of 4)
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const size_t i = (n4 << 2) + threadIdx.x;
+        const float lam = decay_seek(runs, (long long)i).lam;
+        float pi = p[i], vi = MODE != SGD_PLAIN ? v[i] : 0.f;
+        sgd_element<MODE>(pi, g[i], vi, lr, mu, gscale, lam);
+        p[i] = pi;
+        if (MODE != SGD_PLAIN) v[i] = vi;
+    }
+}
+}  // namespace
+
+extern "C" int ssdseg_sgd_step(ssdseg_ctx* ctx, float* params, const float* grads, float* velocity, size_t count, float lr, float momentum,
+                               int nesterov, float grad_scale, const long long* run_end, const float* run_decay, int nruns) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    SSDSEG_ARG(params != nullptr, 2);
+    SSDSEG_ARG(grads != nullptr, 3);
+    SSDSEG_ARG(momentum >= 0.f && momentum < 1.f, 7);
+    SSDSEG_ARG(velocity != nullptr || momentum == 0.f, 4);
+    SSDSEG_DECAY_ARGS(run_end, run_decay, nruns, 10, 11, 12);
+    if (count == 0) return 0;
+    { int jrc = ssdseg_join(ctx); if (jrc) return jrc; }   // weight gradients may still be in flight on the side stream
+    const size_t n4 = count / 4;
+    const unsigned blocks = decay_blocks(n4);
+    const DecayRuns runs = {run_end, run_decay, nruns};
+    const double bytes = (momentum > 0.f ? 20.0 : 12.0) * (double)count + 12.0 * nruns;
+    if (momentum == 0.f)
+        SSDSEG_LAUNCH_NAMED(ctx, "sgd_kernel", bytes, 0.0, sgd_kernel<SGD_PLAIN>, dim3(blocks), dim3(256), 0, params, grads, velocity, n4, count,
+                            lr, momentum, grad_scale, runs);
+    else if (!nesterov)
+        SSDSEG_LAUNCH_NAMED(ctx, "sgd_momentum_kernel", bytes, 0.0, sgd_kernel<SGD_MOMENTUM>, dim3(blocks), dim3(256), 0, params, grads, velocity,
+                            n4, count, lr, momentum, grad_scale, runs);
+    else
+        SSDSEG_LAUNCH_NAMED(ctx, "sgd_nesterov_kernel", bytes, 0.0, sgd_kernel<SGD_NESTEROV>, dim3(blocks), dim3(256), 0, params, grads, velocity,
+                            n4, count, lr, momentum, grad_scale, runs);
+    SSDSEG_LAUNCH_CHECK();
+    return 0;
+}

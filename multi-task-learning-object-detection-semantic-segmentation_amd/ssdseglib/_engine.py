@@ -16,6 +16,7 @@ import numpy as np
 from . import _graph as K
 from . import _hip as H
 from . import layers as L
+from . import optimizers as O
 from ._loss_bind import LossBinding, bind_losses, bind_metrics, launch_metrics  # noqa: F401  (LossBinding: re-exported)
 from ._ops import (ACT_NONE, ACT_RELU, ActBwdOp, ApplyOp, BilinearOp, BNRec, BnOp, ChannelStatsOp, Conv3Op, DecodeNmsOp, DwOp, GapOp,
                    HeadGatherOp, MaskHeadOp, MaxPoolOp, Op, PwOp, ShuffleOp, SoftmaxRowsOp, SplitGatherOp, StemOp, Store, TableShuffleOp,
@@ -785,15 +786,75 @@ class Engine:
         self.backward()
         if allreduce is not None:
             allreduce()
-        o = optimizer
-        self.adam_step(lr=o.learning_rate, beta1=o.beta_1, beta2=o.beta_2, eps=o.epsilon, grad_scale=1.0 / world) if o is not None \
-            else self.adam_step(grad_scale=1.0 / world)
+        self.optimizer_step(optimizer, grad_scale=1.0 / world)
 
-    def adam_step(self, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
+    def optimizer_step(self, o, grad_scale=1.0):
+        """the update of the compiled optimizer `o` (optimizers.Adam / SGD; None: Adam at its defaults here).  A schedule is
+        evaluated at the number of updates already applied -- P["step"] before it is incremented -- in float64; the C call
+        rounds it to float32.  P["lr"] keeps the rate of the last update for fit's history."""
+        if o is None:
+            return self.adam_step(grad_scale=grad_scale)
+        self._restore_optimizer_state()            # before the schedule reads the step counter
+        P = self.P
+        lr = P["lr"] = O.rate_at(o.learning_rate, P.get("step", 0))
+        if isinstance(o, O.SGD):
+            self.sgd_step(lr=lr, momentum=o.momentum, nesterov=o.nesterov, grad_scale=grad_scale, decay=self._decay_table(o))
+        else:
+            self.adam_step(lr=lr, beta1=o.beta_1, beta2=o.beta_2, eps=o.epsilon, grad_scale=grad_scale, decay=self._decay_table(o))
+
+    def _decay_table(self, o):
+        """the optimizer's weight-decay run table over the parameter bucket (optimizers.decay_runs; None without decay): built once
+        per model and (weight_decay, names) from P["index"] in bucket order, uploaded once"""
+        if o.weight_decay == 0.0:
+            return None
+        cache = self.P.setdefault("decay_tables", {})
+        key = (o.weight_decay, o.weight_decay_names)
+        if key not in cache:
+            entries = sorted((off, wname, int(np.prod(shape))) for (_, wname), (which, off, shape) in self.P["index"].items() if which == "params")
+            ends, lams = O.decay_runs([(wname, off, size) for off, wname, size in entries], *key)
+            assert ends.size and ends[-1] == self.P["n_tr"]
+            cache[key] = (self.ctx.array(ends), self.ctx.array(lams), int(ends.size))
+        return cache[key]
+
+    def _restore_optimizer_state(self):
+        """state that optimizers.set_state / load_state left on the model: into the step counter and the state buckets"""
+        pend = self.model.__dict__.pop("_optimizer_state", None)
+        if pend is None:
+            return
+        P = self.P
+        P["step"] = pend["step"]
+        names = {id(l): l.name for l in self.model.layers}
+        flat = {}
+        for (lid, wname), (which, off, shape) in P["index"].items():
+            for slot in ("m", "v", "velocity"):
+                arr = pend["arrays"].get(f"{names[lid]}/{wname}:{slot}") if which == "params" else None
+                if arr is not None:
+                    flat.setdefault(slot, np.zeros(P["n_tr"], np.float32))[off:off + arr.size] = arr.reshape(-1)
+        for slot, host in flat.items():
+            bucket = {"m": "adam_m", "v": "adam_v", "velocity": "velocity"}[slot]
+            if P.get(bucket) is None:
+                P[bucket] = self.ctx.empty(P["n_tr"])
+            P[bucket].upload(host)
+
+    def adam_step(self, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, decay=None):
+        self._restore_optimizer_state()
         P = self.P
         P["step"] = P.get("step", 0) + 1          # shared by every engine (batch size) of the same model
-        self.ctx.call("ssdseg_adam_step", P["params"], P["grads"], P["adam_m"], P["adam_v"], C.c_size_t(P["n_tr"]), lr, beta1, beta2, eps,
-                      P["step"], grad_scale)
+        if decay is None:
+            self.ctx.call("ssdseg_adam_step", P["params"], P["grads"], P["adam_m"], P["adam_v"], C.c_size_t(P["n_tr"]), lr, beta1, beta2, eps,
+                          P["step"], grad_scale)
+        else:
+            self.ctx.call("ssdseg_adamw_step", P["params"], P["grads"], P["adam_m"], P["adam_v"], C.c_size_t(P["n_tr"]), lr, beta1, beta2, eps,
+                          P["step"], grad_scale, *decay)
+
+    def sgd_step(self, lr=0.01, momentum=0.0, nesterov=False, grad_scale=1.0, decay=None):
+        self._restore_optimizer_state()
+        P = self.P
+        P["step"] = P.get("step", 0) + 1
+        if momentum > 0 and P.get("velocity") is None:
+            P["velocity"] = self.ctx.zeros(P["n_tr"])     # allocated on first use: an Adam run never pays for it
+        self.ctx.call("ssdseg_sgd_step", P["params"], P["grads"], P.get("velocity") if momentum > 0 else None, C.c_size_t(P["n_tr"]), lr,
+                      momentum, int(bool(nesterov)), grad_scale, *(decay or (None, None, 0)))
 
 
 _default_ctx: Optional[H.Context] = None

@@ -163,6 +163,9 @@ def run_fit(model: K.Model, data, epochs=1, validation_data=None, verbose=0) -> 
             seen += n
             cur = nxt
         logs = {k: v / max(seen, 1) for k, v in sums.items()}
+        opt = model._compiled.get("optimizer")
+        if seen and opt is not None and callable(getattr(opt, "learning_rate", None)):
+            logs["lr"] = float(np.float32(eng.P["lr"]))      # a scheduled rate: the one of the epoch's last step, as the kernel took it
         if validation_data is not None:
             vs, vseen = {}, 0
             for x, y in _batches(validation_data):

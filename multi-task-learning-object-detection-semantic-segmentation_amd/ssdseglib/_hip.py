@@ -17,6 +17,7 @@ _LIB_NAME = "libssdseg_hip.so"
 _lib = None
 
 ACT_NONE, ACT_RELU, ACT_RELU6, ACT_ZERO = 0, 1, 2, 3
+DECAY_RUNS_MAX = 4096      # SSDSEG_DECAY_RUNS_MAX: the longest weight-decay run table ssdseg_sgd_step / ssdseg_adamw_step take
 
 
 class SsdsegError(RuntimeError):
@@ -154,6 +155,8 @@ _SIGNATURES = {
     "ssdseg_eval_mask_jaccard": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "ssdseg_eval_det_best_iou": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "ssdseg_adam_step": [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _f],
+    "ssdseg_sgd_step": [_vp, _vp, _vp, _vp, _sz, _f, _f, _i, _f, _vp, _vp, _i],
+    "ssdseg_adamw_step": [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _f, _vp, _vp, _i],
     "ssdseg_maxpool3x3s2_fwd": [_vp, _VP, _vp, _i, _i, _i, _i],
     "ssdseg_maxpool3x3s2_bwd": [_vp, _VP, _vp, _vp, _i, _i, _i, _i],
     "ssdseg_channel_shuffle": [_vp, _VP, _i, _vp, _i, _i, _i, _i, _i],
