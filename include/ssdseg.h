@@ -624,6 +624,40 @@ int ssdseg_adamw_step(ssdseg_ctx* ctx, float* params, const float* grads, float*
                       float beta1, float beta2, float eps, int step, float grad_scale, const long long* run_end,
                       const float* run_decay, int nruns);
 
+/* ---------------------------------------------------------------- K20c: gradient clipping and the EMA of the weights
+ * Keras 2.13's `global_clipnorm` (tf.clip_by_global_norm), `clipvalue` (tf.clip_by_value) and `use_ema`, on the device: the clip
+ * factor depends on this step's gradients, so it is produced into device memory and consumed from there -- no download, no stall.
+ *
+ * ssdseg_grad_norm writes two floats:
+ *   out[0] = |grad_scale| * sqrt(sum g_i^2)                     the global norm of the scaled gradient, rounded once to float
+ *   out[1] = norm > clip_norm ? clip_norm / norm : 1            computed in double, rounded once
+ * out[1] is exactly 1.0f when clip_norm <= 0 or not finite, for an all-zero bucket (no 0/0), for count == 0, and for a NaN norm
+ * (the comparison fails; non-finite gradients then reach the weights as they do without clipping -- no step is skipped).
+ * Squares and sums are fp64 (the square of a float is exact in double: no overflow at 1e30, no underflow at 1e-30).  `partials`
+ * is scratch of ssdseg_grad_norm_parts(count) doubles -- a function of count alone, as the partition of the bucket is -- and the
+ * reduction has one fixed order: two launches (blocks write partials, one block folds them), no atomics.  The same bucket gives
+ * the same 8 bytes on every call and on every rank.  The entry joins the side stream first, like the step entries.
+ *
+ * ssdseg_sgd_step_clipped / ssdseg_adamw_step_clipped are ssdseg_sgd_step / ssdseg_adamw_step with
+ *   g' = clampv((g * grad_scale) * s),  clampv(x) = x < -c ? -c : (x > c ? c : x)    (NaN passes through, as tf.clip_by_value)
+ * in place of g' = g * grad_scale; everything after g' is the same element function.  s = *clip_scale (device, one float; NULL: 1),
+ * c = clip_value (> 0; +inf: none; 0, negative or NaN is an argument error).  With *clip_scale == 1 and clip_value == +inf the
+ * result is the unclipped entry's, bit for bit: for SGD at any grad_scale, for AdamW wherever g * grad_scale is exact (a
+ * power-of-two grad_scale) -- the unclipped kernel fuses that product into m's update, elsewhere m differs by its one rounding.
+ *
+ * ssdseg_ema_update: ema += (p - ema) * (1 - momentum), 1 - momentum formed once in float; momentum in [0, 1].  ema == p is a
+ * fixed point.  A 12 B per element pass of its own: it follows any of the three step entries. */
+int ssdseg_grad_norm_parts(size_t count);
+int ssdseg_grad_norm(ssdseg_ctx* ctx, const float* grads, size_t count, float grad_scale, float clip_norm, double* partials,
+                     float* out);
+int ssdseg_sgd_step_clipped(ssdseg_ctx* ctx, float* params, const float* grads, float* velocity, size_t count, float lr,
+                            float momentum, int nesterov, float grad_scale, const long long* run_end, const float* run_decay,
+                            int nruns, const float* clip_scale, float clip_value);
+int ssdseg_adamw_step_clipped(ssdseg_ctx* ctx, float* params, const float* grads, float* m, float* v, size_t count, float lr,
+                              float beta1, float beta2, float eps, int step, float grad_scale, const long long* run_end,
+                              const float* run_decay, int nruns, const float* clip_scale, float clip_value);
+int ssdseg_ema_update(ssdseg_ctx* ctx, float* ema, const float* params, size_t count, float momentum);
+
 /* ---------------------------------------------------------------- K21: ShuffleNetV2-only ops
  * MaxPooling2D 3x3 stride 2 SAME (models.py:629); argmax-free backward (recomputes the window max). */
 int ssdseg_maxpool3x3s2_fwd(ssdseg_ctx* ctx, const ssdseg_view* in, float* out, int n, int h, int wdt, int c);

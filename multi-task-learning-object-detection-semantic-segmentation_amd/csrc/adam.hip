@@ -3,32 +3,37 @@
 // One fused multi-tensor pass over the flat parameter bucket (HBM-bound: 4 streams read, 3 written).
 // AdamW (ssdseg_adamw_step) is the same body with the decoupled decay p -= (lr lambda) p compiled in front of it; lambda comes
 // from the run table (decay_runs.h), which also makes a block's float4s one contiguous chunk instead of a grid-stride comb.
+// ssdseg_adamw_step_clipped (K20c) is the same kernel with g' = clampv((g * grad_scale) * s) compiled in (CLIP; grad_clip.h).
 #include <math.h>
 
 #include "common.h"
 #include "decay_runs.h"
+#include "grad_clip.h"
 
 namespace {
-template <bool DECAY>
+template <bool DECAY, bool CLIP>
 __device__ __forceinline__ void adam_element(float& p, float g, float& m, float& v, float alpha, float one_minus_b1, float one_minus_b2,
-                                             float eps, float gscale, float lr, float lam) {
-    const float gk = g * gscale;
+                                             float eps, float gscale, float lr, float lam, float s, float c) {
+    float gk = g * gscale;
+    if (CLIP) gk = clampv(gk * s, c);
     if (DECAY) p = decay_apply(p, lr, lam);
     m += (gk - m) * one_minus_b1;
     v += (gk * gk - v) * one_minus_b2;
     p -= alpha * m / (sqrtf(v) + eps);
 }
 
-template <bool DECAY>
+template <bool DECAY, bool CLIP>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n4,
-                            size_t n, float alpha, float one_minus_b1, float one_minus_b2, float eps, float gscale, float lr, DecayRuns runs) {
+                            size_t n, float alpha, float one_minus_b1, float one_minus_b2, float eps, float gscale, float lr, DecayRuns runs,
+                            GradClip clip) {
+    const float s = CLIP ? clip_factor(clip) : 1.f, c = clip.value;
     if (!DECAY) {
         const size_t stride = (size_t)gridDim.x * blockDim.x;
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
             float4 pp = ld4(p + 4 * i), gg = ld4(g + 4 * i), mm = ld4(m + 4 * i), vv = ld4(v + 4 * i);
             float* pe = &pp.x; float* ge = &gg.x; float* me = &mm.x; float* ve = &vv.x;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) adam_element<false>(pe[k], ge[k], me[k], ve[k], alpha, one_minus_b1, one_minus_b2, eps, gscale, lr, 0.f);
+            for (int k = 0; k < 4; ++k) adam_element<false, CLIP>(pe[k], ge[k], me[k], ve[k], alpha, one_minus_b1, one_minus_b2, eps, gscale, lr, 0.f, s, c);
             st4(p + 4 * i, pp); st4(m + 4 * i, mm); st4(v + 4 * i, vv);
         }
     } else {
@@ -44,7 +49,7 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
             float lam[4];
             decay_lambda4(runs, cur, (long long)(i << 2), lam);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) adam_element<true>(pe[k], ge[k], me[k], ve[k], alpha, one_minus_b1, one_minus_b2, eps, gscale, lr, lam[k]);
+            for (int k = 0; k < 4; ++k) adam_element<true, CLIP>(pe[k], ge[k], me[k], ve[k], alpha, one_minus_b1, one_minus_b2, eps, gscale, lr, lam[k], s, c);
             st4(p + 4 * i, pp); st4(m + 4 * i, mm); st4(v + 4 * i, vv);
             i += blockDim.x;
             if (i < last) { pp = ld4(p + 4 * i); gg = ld4(g + 4 * i); mm = ld4(m + 4 * i); vv = ld4(v + 4 * i); }
@@ -55,23 +60,26 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
         const size_t i = (n4 << 2) + threadIdx.x;
         const float lam = DECAY ? decay_seek(runs, (long long)i).lam : 0.f;
         float pi = p[i], mi = m[i], vi = v[i];
-        adam_element<DECAY>(pi, g[i], mi, vi, alpha, one_minus_b1, one_minus_b2, eps, gscale, lr, lam);
+        adam_element<DECAY, CLIP>(pi, g[i], mi, vi, alpha, one_minus_b1, one_minus_b2, eps, gscale, lr, lam, s, c);
         p[i] = pi; m[i] = mi; v[i] = vi;
     }
 }
 
+template <bool CLIP>
 int adam_launch(ssdseg_ctx* ctx, float* params, const float* grads, float* m, float* v, size_t count, float lr, float beta1, float beta2,
-                float eps, int step, float grad_scale, const long long* run_end, const float* run_decay, int nruns) {
+                float eps, int step, float grad_scale, const long long* run_end, const float* run_decay, int nruns, GradClip clip) {
     { int jrc = ssdseg_join(ctx); if (jrc) return jrc; }   // weight gradients may still be in flight on the side stream
     const double alpha = (double)lr * sqrt(1.0 - pow((double)beta2, step)) / (1.0 - pow((double)beta1, step));
     const size_t n4 = count / 4;
     const DecayRuns runs = {run_end, run_decay, nruns};
     if (nruns == 0)
-        SSDSEG_LAUNCH_NAMED(ctx, "adam_kernel", 28.0 * (double)count, 0.0, adam_kernel<false>, dim3(optimizer_blocks(n4)), dim3(256), 0, params,
-                            grads, m, v, n4, count, (float)alpha, 1.f - beta1, 1.f - beta2, eps, grad_scale, lr, runs);
+        SSDSEG_LAUNCH_NAMED(ctx, CLIP ? "adam_clipped_kernel" : "adam_kernel", 28.0 * (double)count, 0.0, (adam_kernel<false, CLIP>),
+                            dim3(optimizer_blocks(n4)), dim3(256), 0, params, grads, m, v, n4, count, (float)alpha, 1.f - beta1, 1.f - beta2, eps,
+                            grad_scale, lr, runs, clip);
     else
-        SSDSEG_LAUNCH_NAMED(ctx, "adamw_kernel", 28.0 * (double)count + 12.0 * nruns, 0.0, adam_kernel<true>, dim3(decay_blocks(n4)), dim3(256), 0,
-                            params, grads, m, v, n4, count, (float)alpha, 1.f - beta1, 1.f - beta2, eps, grad_scale, lr, runs);
+        SSDSEG_LAUNCH_NAMED(ctx, CLIP ? "adamw_clipped_kernel" : "adamw_kernel", 28.0 * (double)count + 12.0 * nruns, 0.0,
+                            (adam_kernel<true, CLIP>), dim3(decay_blocks(n4)), dim3(256), 0, params, grads, m, v, n4, count, (float)alpha,
+                            1.f - beta1, 1.f - beta2, eps, grad_scale, lr, runs, clip);
     SSDSEG_LAUNCH_CHECK();
     return 0;
 }
@@ -83,7 +91,7 @@ extern "C" int ssdseg_adam_step(ssdseg_ctx* ctx, float* params, const float* gra
     SSDSEG_ARG(params && grads && m && v, 2);
     SSDSEG_ARG(step >= 1, 11);
     if (count == 0) return 0;
-    return adam_launch(ctx, params, grads, m, v, count, lr, beta1, beta2, eps, step, grad_scale, nullptr, nullptr, 0);
+    return adam_launch<false>(ctx, params, grads, m, v, count, lr, beta1, beta2, eps, step, grad_scale, nullptr, nullptr, 0, GradClip{nullptr, 0.f});
 }
 
 extern "C" int ssdseg_adamw_step(ssdseg_ctx* ctx, float* params, const float* grads, float* m, float* v, size_t count, float lr,
@@ -94,5 +102,19 @@ extern "C" int ssdseg_adamw_step(ssdseg_ctx* ctx, float* params, const float* gr
     SSDSEG_ARG(step >= 1, 11);
     SSDSEG_DECAY_ARGS(run_end, run_decay, nruns, 13, 14, 15);
     if (count == 0) return 0;
-    return adam_launch(ctx, params, grads, m, v, count, lr, beta1, beta2, eps, step, grad_scale, run_end, run_decay, nruns);
+    return adam_launch<false>(ctx, params, grads, m, v, count, lr, beta1, beta2, eps, step, grad_scale, run_end, run_decay, nruns,
+                              GradClip{nullptr, 0.f});
+}
+
+extern "C" int ssdseg_adamw_step_clipped(ssdseg_ctx* ctx, float* params, const float* grads, float* m, float* v, size_t count, float lr,
+                                         float beta1, float beta2, float eps, int step, float grad_scale, const long long* run_end,
+                                         const float* run_decay, int nruns, const float* clip_scale, float clip_value) {
+    SSDSEG_ARG(ctx != nullptr, 1);
+    SSDSEG_ARG(params && grads && m && v, 2);
+    SSDSEG_ARG(step >= 1, 11);
+    SSDSEG_DECAY_ARGS(run_end, run_decay, nruns, 13, 14, 15);
+    SSDSEG_ARG(clip_value > 0.f, 17);                      // +inf: no clamp; fails for NaN
+    if (count == 0) return 0;
+    return adam_launch<true>(ctx, params, grads, m, v, count, lr, beta1, beta2, eps, step, grad_scale, run_end, run_decay, nruns,
+                             GradClip{clip_scale, clip_value});
 }

@@ -8,6 +8,7 @@ its input and target buffers; fit / predict / evaluate are `_fit`.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -777,6 +778,7 @@ class Engine:
         return out
 
     def train_step(self, images=None, targets=None, optimizer=None, allreduce=None, world=1):
+        self._not_averaging()
         if images is not None:
             self.set_input(images)
         if targets is not None:
@@ -791,16 +793,46 @@ class Engine:
     def optimizer_step(self, o, grad_scale=1.0):
         """the update of the compiled optimizer `o` (optimizers.Adam / SGD; None: Adam at its defaults here).  A schedule is
         evaluated at the number of updates already applied -- P["step"] before it is incremented -- in float64; the C call
-        rounds it to float32.  P["lr"] keeps the rate of the last update for fit's history."""
+        rounds it to float32.  P["lr"] keeps the rate of the last update for fit's history.
+        Clipping and the EMA (optimizers._Optimizer._clip_and_ema) stay on the device: the norm entry leaves its factor in P["clip"],
+        the *_clipped step reads it from there, and the EMA pass follows the step -- all queued, nothing downloaded."""
+        self._not_averaging()
         if o is None:
             return self.adam_step(grad_scale=grad_scale)
         self._restore_optimizer_state()            # before the schedule reads the step counter
         P = self.P
         lr = P["lr"] = O.rate_at(o.learning_rate, P.get("step", 0))
+        clip = self._clip_args(o, grad_scale)
+        if o.use_ema and P.get("ema") is None:
+            P["ema"] = self.ctx.empty(P["n_tr"]).copy_from(P["params"])      # the average starts as the weights before the first update
         if isinstance(o, O.SGD):
-            self.sgd_step(lr=lr, momentum=o.momentum, nesterov=o.nesterov, grad_scale=grad_scale, decay=self._decay_table(o))
+            self.sgd_step(lr=lr, momentum=o.momentum, nesterov=o.nesterov, grad_scale=grad_scale, decay=self._decay_table(o), clip=clip)
         else:
-            self.adam_step(lr=lr, beta1=o.beta_1, beta2=o.beta_2, eps=o.epsilon, grad_scale=grad_scale, decay=self._decay_table(o))
+            self.adam_step(lr=lr, beta1=o.beta_1, beta2=o.beta_2, eps=o.epsilon, grad_scale=grad_scale, decay=self._decay_table(o), clip=clip)
+        if o.use_ema:
+            self.ctx.call("ssdseg_ema_update", P["ema"], P["params"], C.c_size_t(P["n_tr"]), o.ema_momentum)
+            if o.ema_overwrite_frequency and P["step"] % o.ema_overwrite_frequency == 0:
+                P["params"].copy_from(P["ema"])
+
+    def _not_averaging(self):
+        if self.P.get("averaging"):
+            raise RuntimeError("no training step inside optimizers.averaged_weights: the parameter bucket holds the averaged weights")
+
+    def _clip_args(self, o, grad_scale):
+        """(device pointer to the clip factor or None, clip value) for the *_clipped step entries; None when the optimizer does not
+        clip -- the step then makes the calls it made before there was clipping.  With global_clipnorm the norm entry is queued here:
+        P["clip"] = {norm, factor}, with its partials allocated on first use."""
+        if o.global_clipnorm is None and o.clipvalue is None:
+            return None
+        if o.global_clipnorm is None:
+            return None, o.clipvalue
+        P = self.P
+        n = C.c_size_t(P["n_tr"])
+        if P.get("clip") is None:
+            P["clip"] = self.ctx.zeros(2)
+            P["clip_parts"] = self.ctx.empty(max(self.ctx.lib.ssdseg_grad_norm_parts(P["n_tr"]), 1), np.float64)
+        self.ctx.call("ssdseg_grad_norm", P["grads"], n, grad_scale, o.global_clipnorm, P["clip_parts"], P["clip"])
+        return P["clip"].view(1, (1,)), math.inf
 
     def _decay_table(self, o):
         """the optimizer's weight-decay run table over the parameter bucket (optimizers.decay_runs; None without decay): built once
@@ -817,44 +849,53 @@ class Engine:
         return cache[key]
 
     def _restore_optimizer_state(self):
-        """state that optimizers.set_state / load_state left on the model: into the step counter and the state buckets"""
-        pend = self.model.__dict__.pop("_optimizer_state", None)
-        if pend is None:
-            return
-        P = self.P
-        P["step"] = pend["step"]
-        names = {id(l): l.name for l in self.model.layers}
-        flat = {}
-        for (lid, wname), (which, off, shape) in P["index"].items():
-            for slot in ("m", "v", "velocity"):
-                arr = pend["arrays"].get(f"{names[lid]}/{wname}:{slot}") if which == "params" else None
-                if arr is not None:
-                    flat.setdefault(slot, np.zeros(P["n_tr"], np.float32))[off:off + arr.size] = arr.reshape(-1)
-        for slot, host in flat.items():
-            bucket = {"m": "adam_m", "v": "adam_v", "velocity": "velocity"}[slot]
-            if P.get(bucket) is None:
-                P[bucket] = self.ctx.empty(P["n_tr"])
-            P[bucket].upload(host)
+        restore_optimizer_state(self.model, self.P)
 
-    def adam_step(self, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, decay=None):
+    def adam_step(self, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, decay=None, clip=None):
         self._restore_optimizer_state()
         P = self.P
         P["step"] = P.get("step", 0) + 1          # shared by every engine (batch size) of the same model
-        if decay is None:
+        if clip is not None:
+            self.ctx.call("ssdseg_adamw_step_clipped", P["params"], P["grads"], P["adam_m"], P["adam_v"], C.c_size_t(P["n_tr"]), lr, beta1, beta2,
+                          eps, P["step"], grad_scale, *(decay or (None, None, 0)), *clip)
+        elif decay is None:
             self.ctx.call("ssdseg_adam_step", P["params"], P["grads"], P["adam_m"], P["adam_v"], C.c_size_t(P["n_tr"]), lr, beta1, beta2, eps,
                           P["step"], grad_scale)
         else:
             self.ctx.call("ssdseg_adamw_step", P["params"], P["grads"], P["adam_m"], P["adam_v"], C.c_size_t(P["n_tr"]), lr, beta1, beta2, eps,
                           P["step"], grad_scale, *decay)
 
-    def sgd_step(self, lr=0.01, momentum=0.0, nesterov=False, grad_scale=1.0, decay=None):
+    def sgd_step(self, lr=0.01, momentum=0.0, nesterov=False, grad_scale=1.0, decay=None, clip=None):
         self._restore_optimizer_state()
         P = self.P
         P["step"] = P.get("step", 0) + 1
         if momentum > 0 and P.get("velocity") is None:
             P["velocity"] = self.ctx.zeros(P["n_tr"])     # allocated on first use: an Adam run never pays for it
-        self.ctx.call("ssdseg_sgd_step", P["params"], P["grads"], P.get("velocity") if momentum > 0 else None, C.c_size_t(P["n_tr"]), lr,
-                      momentum, int(bool(nesterov)), grad_scale, *(decay or (None, None, 0)))
+        self.ctx.call("ssdseg_sgd_step" if clip is None else "ssdseg_sgd_step_clipped", P["params"], P["grads"],
+                      P.get("velocity") if momentum > 0 else None, C.c_size_t(P["n_tr"]), lr, momentum, int(bool(nesterov)), grad_scale,
+                      *(decay or (None, None, 0)), *(clip or ()))
+
+
+def restore_optimizer_state(model, P):
+    """state that optimizers.set_state / load_state left on `model`: into the step counter and the state buckets of its parameter
+    set P (the averaged weights, slot `ema`, included)"""
+    pend = model.__dict__.pop("_optimizer_state", None)
+    if pend is None:
+        return
+    ctx = P["params"].ctx
+    P["step"] = pend["step"]
+    names = {id(l): l.name for l in model.layers}
+    flat = {}
+    for (lid, wname), (which, off, shape) in P["index"].items():
+        for slot in O.BUCKETS:
+            arr = pend["arrays"].get(f"{names[lid]}/{wname}:{slot}") if which == "params" else None
+            if arr is not None:
+                flat.setdefault(slot, np.zeros(P["n_tr"], np.float32))[off:off + arr.size] = arr.reshape(-1)
+    for slot, host in flat.items():
+        bucket = O.BUCKETS[slot]
+        if P.get(bucket) is None:
+            P[bucket] = ctx.empty(P["n_tr"])
+        P[bucket].upload(host)
 
 
 _default_ctx: Optional[H.Context] = None

@@ -157,6 +157,11 @@ _SIGNATURES = {
     "ssdseg_adam_step": [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _f],
     "ssdseg_sgd_step": [_vp, _vp, _vp, _vp, _sz, _f, _f, _i, _f, _vp, _vp, _i],
     "ssdseg_adamw_step": [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _f, _vp, _vp, _i],
+    "ssdseg_grad_norm_parts": [_sz],           # returns the number of partials itself
+    "ssdseg_grad_norm": [_vp, _vp, _sz, _f, _f, _vp, _vp],
+    "ssdseg_sgd_step_clipped": [_vp, _vp, _vp, _vp, _sz, _f, _f, _i, _f, _vp, _vp, _i, _vp, _f],
+    "ssdseg_adamw_step_clipped": [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _f, _vp, _vp, _i, _vp, _f],
+    "ssdseg_ema_update": [_vp, _vp, _vp, _sz, _f],
     "ssdseg_maxpool3x3s2_fwd": [_vp, _VP, _vp, _i, _i, _i, _i],
     "ssdseg_maxpool3x3s2_bwd": [_vp, _VP, _vp, _vp, _i, _i, _i, _i],
     "ssdseg_channel_shuffle": [_vp, _VP, _i, _vp, _i, _i, _i, _i, _i],

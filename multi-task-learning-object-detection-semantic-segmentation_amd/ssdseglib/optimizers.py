@@ -6,6 +6,10 @@ decay 5e-4, stepped rate; DeepLabV3+: momentum and the "poly" rate; MobileNetV2:
 take Keras 2.13's decoupled `weight_decay`, applied to the weights named in `weight_decay_names`.  The updates themselves are
 the fused HIP kernels ssdseg_adam_step / ssdseg_adamw_step / ssdseg_sgd_step over the flat parameter bucket (include/ssdseg.h);
 `_sgd_reference` and `_adamw_reference` below are their specification, as `datacoder._mosaic_resample` is the mosaic kernel's.
+Both also take Keras' `global_clipnorm` / `clipvalue` and `use_ema` / `ema_momentum` / `ema_overwrite_frequency`: the clip factor is
+produced and consumed on the device (ssdseg_grad_norm, then ssdseg_sgd_step_clipped / ssdseg_adamw_step_clipped), the average is
+a pass after the step (ssdseg_ema_update); `_clip_reference` and `_ema_reference` are their specifications, and
+`averaged_weights` / `finalize_variable_values` put the average where predict, evaluate and Model.save see it.
 
 A learning rate is a float or a schedule: a callable `step -> float`, evaluated on the host in float64 with `step` = the number
 of updates already applied (0 for the first), and rounded once to float32 where it is handed to the kernel.
@@ -101,25 +105,55 @@ class _Optimizer:
         if self.weight_decay < 0:
             raise ValueError("weight_decay must not be negative")
 
+    def _clip_and_ema(self, global_clipnorm, clipvalue, use_ema, ema_momentum, ema_overwrite_frequency, clipnorm):
+        """the base-class arguments of Keras 2.13's optimizers that act on the gradient before, and on the weights after, the update:
+            global_clipnorm : g' = g * min(1, global_clipnorm / ||g||) over ALL gradients (tf.clip_by_global_norm)
+            clipvalue       : g' = clip(g, -clipvalue, clipvalue) elementwise (tf.clip_by_value)
+            use_ema         : ema = ema_momentum * ema + (1 - ema_momentum) * p after every update, ema = p before the first;
+                              with ema_overwrite_frequency = k the weights take the average after every k-th update
+        The gradient is the one after `grad_scale` (the mean over the ranks); the clip comes before the decay and the update."""
+        if clipnorm is not None:
+            raise NotImplementedError("clipnorm (the per-variable norm) is not implemented: use global_clipnorm, the norm over all gradients")
+        self.global_clipnorm = None if global_clipnorm is None else float(global_clipnorm)
+        self.clipvalue = None if clipvalue is None else float(clipvalue)
+        for name in ("global_clipnorm", "clipvalue"):
+            v = getattr(self, name)
+            if v is not None and not v > 0:
+                raise ValueError(f"{name} must be positive")
+        if self.global_clipnorm is not None and self.clipvalue is not None:
+            raise ValueError("at most one of global_clipnorm and clipvalue may be set")
+        self.use_ema, self.ema_momentum = bool(use_ema), float(ema_momentum)
+        if not 0.0 <= self.ema_momentum <= 1.0:
+            raise ValueError("ema_momentum must be in [0, 1]")
+        if ema_overwrite_frequency is not None and (isinstance(ema_overwrite_frequency, bool) or not isinstance(ema_overwrite_frequency, (int, np.integer))
+                                                    or ema_overwrite_frequency < 1):
+            raise ValueError("ema_overwrite_frequency must be a positive int or None")
+        self.ema_overwrite_frequency = None if ema_overwrite_frequency is None else int(ema_overwrite_frequency)
+
 
 class Adam(_Optimizer):
     """Keras 2.13 Adam; with weight_decay > 0, p -= learning_rate * weight_decay * p on the `weight_decay_names` weights first
-    (the rate itself, not the bias-corrected one)."""
+    (the rate itself, not the bias-corrected one).  Clipping and EMA: `_Optimizer._clip_and_ema`."""
     kind, slots = "adam", ("m", "v")
 
     def __init__(self, learning_rate=1e-3, beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, weight_decay: float = 0.0,
-                 weight_decay_names=DECAY_NAMES):
+                 weight_decay_names=DECAY_NAMES, global_clipnorm=None, clipvalue=None, use_ema: bool = False, ema_momentum: float = 0.99,
+                 ema_overwrite_frequency=None, clipnorm=None):
         self._common(learning_rate, weight_decay, weight_decay_names)
+        self._clip_and_ema(global_clipnorm, clipvalue, use_ema, ema_momentum, ema_overwrite_frequency, clipnorm)
         self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
 
 
 class SGD(_Optimizer):
-    """Keras 2.13 SGD: v = momentum v - lr g, p += v (Nesterov: p += momentum v - lr g); momentum 0: p -= lr g.  weight_decay as Adam's."""
+    """Keras 2.13 SGD: v = momentum v - lr g, p += v (Nesterov: p += momentum v - lr g); momentum 0: p -= lr g.  weight_decay as Adam's.
+    Clipping and EMA: `_Optimizer._clip_and_ema`."""
     kind = "sgd"
 
     def __init__(self, learning_rate=0.01, momentum: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0,
-                 weight_decay_names=DECAY_NAMES):
+                 weight_decay_names=DECAY_NAMES, global_clipnorm=None, clipvalue=None, use_ema: bool = False, ema_momentum: float = 0.99,
+                 ema_overwrite_frequency=None, clipnorm=None):
         self._common(learning_rate, weight_decay, weight_decay_names)
+        self._clip_and_ema(global_clipnorm, clipvalue, use_ema, ema_momentum, ema_overwrite_frequency, clipnorm)
         self.momentum, self.nesterov = float(momentum), bool(nesterov)
         if not 0.0 <= self.momentum < 1.0:
             raise ValueError("momentum must be in [0, 1)")
@@ -188,10 +222,35 @@ def _decayed(p, lr, run_end, run_decay):
     return p - (p.dtype.type(lr) * lam) * p
 
 
-def _sgd_reference(p, g, v, lr, momentum=0.0, nesterov=False, grad_scale=1.0, run_end=None, run_decay=None):
-    """ssdseg_sgd_step in NumPy, in the dtype of `p` -> (p, v); v may be None when momentum == 0 and comes back as it went in"""
+def _clip_reference(g, grad_scale=1.0, global_clipnorm=None):
+    """ssdseg_grad_norm in float64 -> (norm, factor): norm = |grad_scale| sqrt(sum g^2) over ALL of `g`, factor = global_clipnorm / norm
+    where the norm exceeds a positive, finite global_clipnorm, and 1 otherwise (also for a zero or a NaN norm)"""
+    g = np.asarray(g, np.float64).reshape(-1)
+    norm = abs(float(grad_scale)) * math.sqrt(float(np.dot(g, g)))
+    c = 0.0 if global_clipnorm is None else float(global_clipnorm)
+    return norm, (c / norm if c > 0 and math.isfinite(c) and norm > c else 1.0)
+
+
+def _clipped(gk, clip_scale, clip_value):
+    """g' = clampv(gk * s, c) of the *_clipped entries, in the dtype of `gk`; NaN passes through; the defaults change nothing"""
+    t = gk.dtype.type
+    if clip_scale == 1.0 and clip_value == math.inf:
+        return gk
+    x, c = gk * t(clip_scale), t(clip_value)
+    return np.where(x < -c, -c, np.where(x > c, c, x))
+
+
+def _ema_reference(ema, p, momentum):
+    """ssdseg_ema_update in NumPy, in the dtype of `ema`: ema + (p - ema) (1 - momentum), 1 - momentum formed once in float32"""
+    t = ema.dtype.type
+    return ema + (p.astype(ema.dtype) - ema) * t(np.float32(1.0) - np.float32(momentum))
+
+
+def _sgd_reference(p, g, v, lr, momentum=0.0, nesterov=False, grad_scale=1.0, run_end=None, run_decay=None, clip_scale=1.0, clip_value=math.inf):
+    """ssdseg_sgd_step in NumPy, in the dtype of `p` -> (p, v); v may be None when momentum == 0 and comes back as it went in.
+    With clip_scale / clip_value: ssdseg_sgd_step_clipped."""
     t = p.dtype.type
-    gk = g.astype(p.dtype) * t(grad_scale)
+    gk = _clipped(g.astype(p.dtype) * t(grad_scale), clip_scale, clip_value)
     p1 = _decayed(p, lr, run_end, run_decay)
     if momentum == 0:
         return p1 - t(lr) * gk, v
@@ -199,10 +258,12 @@ def _sgd_reference(p, g, v, lr, momentum=0.0, nesterov=False, grad_scale=1.0, ru
     return (p1 + (t(momentum) * v - t(lr) * gk) if nesterov else p1 + v), v
 
 
-def _adamw_reference(p, g, m, v, step, lr=1e-3, b1=0.9, b2=0.999, eps=1e-7, grad_scale=1.0, run_end=None, run_decay=None):
-    """ssdseg_adamw_step in NumPy, in the dtype of `p` -> (p, m, v); `step` counts from 1, as the kernel's"""
+def _adamw_reference(p, g, m, v, step, lr=1e-3, b1=0.9, b2=0.999, eps=1e-7, grad_scale=1.0, run_end=None, run_decay=None, clip_scale=1.0,
+                     clip_value=math.inf):
+    """ssdseg_adamw_step in NumPy, in the dtype of `p` -> (p, m, v); `step` counts from 1, as the kernel's.
+    With clip_scale / clip_value: ssdseg_adamw_step_clipped."""
     t = p.dtype.type
-    gk = g.astype(p.dtype) * t(grad_scale)
+    gk = _clipped(g.astype(p.dtype) * t(grad_scale), clip_scale, clip_value)
     p1 = _decayed(p, lr, run_end, run_decay)
     m = m + (gk - m) * t(1.0 - b1)
     v = v + (gk * gk - v) * t(1.0 - b2)
@@ -211,6 +272,14 @@ def _adamw_reference(p, g, m, v, step, lr=1e-3, b1=0.9, b2=0.999, eps=1e-7, grad
 
 
 # ===================================================================================================== checkpoint
+BUCKETS = {"m": "adam_m", "v": "adam_v", "velocity": "velocity", "ema": "ema"}      # state slot -> the engine's bucket
+
+
+def state_slots(opt):
+    """the optimizer's slots plus `ema`, the averaged weights, when it keeps them"""
+    return tuple(opt.slots) + (("ema",) if opt.use_ema else ())
+
+
 def _compiled_optimizer(model):
     comp = getattr(model, "_compiled", None)
     if not comp or comp.get("optimizer") is None:
@@ -220,20 +289,23 @@ def _compiled_optimizer(model):
 
 def get_state(model):
     """-> (kind, step, {`<layer>/<weight>:<slot>`: array}) of the model's compiled optimizer: from the device once the model has
-    trained, otherwise what `set_state` left for the first step, otherwise the initial state (step 0, zeros)"""
+    trained, otherwise what `set_state` left for the first step, otherwise the initial state (step 0, zeros; `:ema`, which only an
+    optimizer with use_ema has: the weights)"""
     opt = _compiled_optimizer(model)
     pending = model.__dict__.get("_optimizer_state")
     if pending is not None:
         return pending["kind"], pending["step"], {k: a.copy() for k, a in pending["arrays"].items()}
     P = getattr(model, "_engine_params", None)
     arrays = {}
-    buckets = {"m": "adam_m", "v": "adam_v", "velocity": "velocity"}
-    for slot in opt.slots:
-        buf = P.get(buckets[slot]) if P is not None else None
+    for slot in state_slots(opt):
+        buf = P.get(BUCKETS[slot]) if P is not None else None
+        if buf is None and slot == "ema" and P is not None:
+            buf = P["params"]                      # no update yet: the average starts as the weights (Keras initialises it from the variable)
         flat = buf.download().reshape(-1) if buf is not None else None
         for l, wname, off, size in bucket_entries(model):
             shape = l.weights[wname].shape
-            arrays[f"{l.name}/{wname}:{slot}"] = (flat[off:off + size].reshape(shape).copy() if flat is not None else np.zeros(shape, np.float32))
+            initial = np.array(l.weights[wname], np.float32) if slot == "ema" else np.zeros(shape, np.float32)
+            arrays[f"{l.name}/{wname}:{slot}"] = flat[off:off + size].reshape(shape).copy() if flat is not None else initial
     return opt.kind, int(P.get("step", 0)) if P is not None else 0, arrays
 
 
@@ -245,7 +317,7 @@ def set_state(model, kind: str, step: int, arrays) -> None:
         raise ValueError(f"optimizer state of kind {kind!r} for a model compiled with {opt.kind!r}")
     kept = {}
     for l, wname, _, _ in bucket_entries(model):
-        for slot in opt.slots:
+        for slot in state_slots(opt):
             key = f"{l.name}/{wname}:{slot}"
             if key not in arrays:
                 raise KeyError(f"optimizer state has no {key}")
@@ -262,7 +334,8 @@ def _npz(path) -> str:
 
 def save_state(model, path) -> None:
     """the optimizer's part of a checkpoint, next to `Model.save`: one .npz with `step`, `kind` and the state arrays keyed
-    `<layer>/<weight>:m`, `:v` (Adam) or `:velocity` (SGD with momentum) -- names and shapes, not the bucket layout"""
+    `<layer>/<weight>:m`, `:v` (Adam) or `:velocity` (SGD with momentum), and `:ema` with use_ema -- names and shapes, not the
+    bucket layout"""
     kind, step, arrays = get_state(model)
     np.savez(_npz(path), step=np.int64(step), kind=np.asarray(kind), **arrays)
 
@@ -275,3 +348,60 @@ def load_state(model, path) -> None:
         if key not in data.files:
             raise KeyError(f"{path}: not an optimizer state file (no {key})")
     set_state(model, str(data["kind"]), int(data["step"]), {k: data[k] for k in data.files if k not in ("step", "kind")})
+
+
+# ===================================================================================================== averaged weights
+def _ema_buckets(model):
+    """(P, the EMA bucket) of a model whose optimizer keeps averaged weights; state that `set_state` left is applied first.  Before
+    the first update there is no bucket (None): the average IS the weights then."""
+    opt = _compiled_optimizer(model)
+    if not opt.use_ema:
+        raise ValueError("the compiled optimizer keeps no averaged weights: build it with use_ema=True")
+    P = getattr(model, "_engine_params", None)
+    if P is None:
+        if model.__dict__.get("_optimizer_state") is not None:
+            raise RuntimeError("the restored averaged weights reach the device with the model's first engine: call predict or train once")
+        return None, None
+    from . import _engine
+    _engine.restore_optimizer_state(model, P)
+    return P, P.get("ema")
+
+
+def finalize_variable_values(model) -> None:
+    """Keras' `optimizer.finalize_variable_values`: the weights become the averaged weights, for good"""
+    P, ema = _ema_buckets(model)
+    if ema is not None:
+        if P.get("averaging"):
+            raise RuntimeError("inside averaged_weights the weights are the average already")
+        P["params"].copy_from(ema)
+
+
+class averaged_weights:
+    """`with averaged_weights(model):` -- inside, the parameter bucket holds the EMA, so predict, evaluate_on_device and Model.save
+    see the averaged weights; the raw weights wait in a backup bucket (allocated on first use) and are back bit for bit on exit,
+    also when the block raises.  Copies, not a pointer swap: every view into the bucket is an address.  BatchNorm's moving
+    statistics are not averaged.  A training step inside the block raises."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def __enter__(self):
+        self.P, ema = _ema_buckets(self.model)
+        if ema is None:
+            self.P = None                          # no update yet: the weights are the average
+            return self.model
+        P = self.P
+        if P.get("averaging"):
+            raise RuntimeError("averaged_weights blocks do not nest")
+        if P.get("ema_backup") is None:
+            P["ema_backup"] = P["params"].ctx.empty(P["n_tr"])
+        P["ema_backup"].copy_from(P["params"])
+        P["params"].copy_from(ema)
+        P["averaging"] = True
+        return self.model
+
+    def __exit__(self, *exc):
+        if self.P is not None:
+            self.P["params"].copy_from(self.P["ema_backup"])
+            self.P["averaging"] = False
+        return False
