@@ -110,13 +110,16 @@ void ssdseg_defer_hold(ssdseg_ctx* ctx, int delta);
         if (_e != hipSuccess) return ssdseg_hip_fail(_e, #call); \
     } while (0)
 
-#define SSDSEG_ARG(cond, n)                                               \
+#define SSDSEG_ARG_TEXT(entry, cond, n, text)                             \
     do {                                                                  \
         if (!(cond)) {                                                    \
-            ssdseg_set_error("%s: invalid argument %d (%s)", __func__, (n), #cond); \
+            ssdseg_set_error("%s: invalid argument %d (%s)", (entry), (n), text); \
             return SSDSEG_EINVAL(n);                                      \
         }                                                                 \
     } while (0)
+#define SSDSEG_ARG(cond, n) SSDSEG_ARG_TEXT(__func__, cond, n, #cond)
+// in a checked function that several entries share: reported under the entry's name
+#define SSDSEG_ARG_AS(entry, cond, n) SSDSEG_ARG_TEXT(entry, cond, n, #cond)
 
 #define SSDSEG_LAUNCH_CHECK()                                   \
     do {                                                        \

@@ -89,15 +89,36 @@ __device__ __forceinline__ void decay_chunk(size_t n4, size_t* first, size_t* la
     *first = a < n4 ? a : n4;
     *last = b < n4 ? b : n4;
 }
+
+// One block's walk over its chunk.  W is the kernel's float4 step: it keeps a float4 per stream in registers and has load(i),
+// apply(lam[4]) and store(i), i a float4 index.
+template <class W>
+__device__ __forceinline__ void decay_walk(const DecayRuns& runs, size_t n4, W& w) {
+    size_t first, last;
+    decay_chunk(n4, &first, &last);
+    size_t i = first + threadIdx.x;
+    // the first float4s are requested BEFORE the seek: its dependent scalar loads then run under loads the block waits for anyway
+    if (i < last) w.load(i);
+    DecayCursor cur = decay_seek(runs, (long long)(first << 2));
+    while (i < last) {
+        float lam[4];
+        decay_lambda4(runs, cur, (long long)(i << 2), lam);
+        w.apply(lam);
+        w.store(i);
+        i += blockDim.x;
+        if (i < last) w.load(i);
+    }
+}
 #endif
 
-// host side: the run-table argument checks shared by the entries (argument numbers of run_end, run_decay, nruns)
-#define SSDSEG_DECAY_ARGS(run_end, run_decay, nruns, a_end, a_decay, a_n)  \
-    do {                                                                    \
-        SSDSEG_ARG((nruns) >= 0, a_n);                                      \
-        SSDSEG_ARG((nruns) == 0 || (run_end) != nullptr, a_end);            \
-        SSDSEG_ARG((nruns) == 0 || (run_decay) != nullptr, a_decay);        \
-        SSDSEG_ARG((nruns) <= SSDSEG_DECAY_RUNS_MAX, a_n);                  \
+// host side: the run-table argument checks shared by the entries (argument numbers of run_end, run_decay, nruns), reported under
+// the name `entry`
+#define SSDSEG_DECAY_ARGS(entry, run_end, run_decay, nruns, a_end, a_decay, a_n)  \
+    do {                                                                           \
+        SSDSEG_ARG_AS(entry, (nruns) >= 0, a_n);                                   \
+        SSDSEG_ARG_AS(entry, (nruns) == 0 || (run_end) != nullptr, a_end);         \
+        SSDSEG_ARG_AS(entry, (nruns) == 0 || (run_decay) != nullptr, a_decay);     \
+        SSDSEG_ARG_AS(entry, (nruns) <= SSDSEG_DECAY_RUNS_MAX, a_n);               \
     } while (0)
 
 // grid of a grid-stride optimizer kernel: a thread per float4, at most 2048 blocks of 256 (csrc/adam.hip)

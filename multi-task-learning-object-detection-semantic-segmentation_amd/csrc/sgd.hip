@@ -26,28 +26,27 @@ __device__ __forceinline__ void sgd_element(float& p, float g, float& v, float l
     }
 }
 
+// the float4 step of decay_walk (decay_runs.h)
+template <int MODE, bool CLIP>
+struct SgdWalk {
+    float* p; const float* g; float* v;
+    float lr, mu, gscale, s, c;
+    float4 pp, gg, vv;
+    __device__ __forceinline__ void load(size_t i) { pp = ld4(p + 4 * i); gg = ld4(g + 4 * i); if (MODE != SGD_PLAIN) vv = ld4(v + 4 * i); }
+    __device__ __forceinline__ void apply(const float lam[4]) {
+        float* pe = &pp.x; float* ge = &gg.x; float* ve = &vv.x;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sgd_element<MODE, CLIP>(pe[k], ge[k], ve[k], lr, mu, gscale, lam[k], s, c);
+    }
+    __device__ __forceinline__ void store(size_t i) { st4(p + 4 * i, pp); if (MODE != SGD_PLAIN) st4(v + 4 * i, vv); }
+};
+
 template <int MODE, bool CLIP>
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v, size_t n4, size_t n, float lr, float mu,
                            float gscale, DecayRuns runs, GradClip clip) {
     const float s = CLIP ? clip_factor(clip) : 1.f, c = clip.value;
-    size_t first, last;
-    decay_chunk(n4, &first, &last);
-    size_t i = first + threadIdx.x;
-    float4 pp = f4(0.f), gg = f4(0.f), vv = f4(0.f);
-    // the first float4s are requested BEFORE the seek: its dependent scalar loads then run under loads the block waits for anyway
-    if (i < last) { pp = ld4(p + 4 * i); gg = ld4(g + 4 * i); if (MODE != SGD_PLAIN) vv = ld4(v + 4 * i); }
-    DecayCursor cur = decay_seek(runs, (long long)(first << 2));
-    while (i < last) {
-        float* pe = &pp.x; float* ge = &gg.x; float* ve = &vv.x;
-        float lam[4];
-        decay_lambda4(runs, cur, (long long)(i << 2), lam);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) sgd_element<MODE, CLIP>(pe[k], ge[k], ve[k], lr, mu, gscale, lam[k], s, c);
-        st4(p + 4 * i, pp);
-        if (MODE != SGD_PLAIN) st4(v + 4 * i, vv);
-        i += blockDim.x;
-        if (i < last) { pp = ld4(p + 4 * i); gg = ld4(g + 4 * i); if (MODE != SGD_PLAIN) vv = ld4(v + 4 * i); }
-    }
+    SgdWalk<MODE, CLIP> w = {p, g, v, lr, mu, gscale, s, c, f4(0.f), f4(0.f), f4(0.f)};
+    decay_walk(runs, n4, w);
     // tail (n not a multiple of 4)
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const size_t i = (n4 << 2) + threadIdx.x;
@@ -58,13 +57,25 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
         if (MODE != SGD_PLAIN) v[i] = vi;
     }
 }
+// what both entries share: the argument checks, reported under the entry's name, then the launch.  clip_value is the 14th
+// argument of the clipped entry.
 template <bool CLIP>
-int sgd_launch(ssdseg_ctx* ctx, float* params, const float* grads, float* velocity, size_t count, float lr, float momentum, int nesterov,
-               float grad_scale, const long long* run_end, const float* run_decay, int nruns, GradClip clip) {
+int sgd_launch(const char* entry, ssdseg_ctx* ctx, float* params, const float* grads, float* velocity, size_t count, float lr, float momentum,
+               int nesterov, float grad_scale, const long long* run_end, const float* run_decay, int nruns, const float* clip_scale,
+               float clip_value) {
+    SSDSEG_ARG_AS(entry, ctx != nullptr, 1);
+    SSDSEG_ARG_AS(entry, params != nullptr, 2);
+    SSDSEG_ARG_AS(entry, grads != nullptr, 3);
+    SSDSEG_ARG_AS(entry, momentum >= 0.f && momentum < 1.f, 7);
+    SSDSEG_ARG_AS(entry, velocity != nullptr || momentum == 0.f, 4);
+    SSDSEG_DECAY_ARGS(entry, run_end, run_decay, nruns, 10, 11, 12);
+    if (CLIP) SSDSEG_ARG_AS(entry, clip_value > 0.f, 14);   // +inf: no clamp; fails for NaN
+    if (count == 0) return 0;
     { int jrc = ssdseg_join(ctx); if (jrc) return jrc; }   // weight gradients may still be in flight on the side stream
     const size_t n4 = count / 4;
     const unsigned blocks = decay_blocks(n4);
     const DecayRuns runs = {run_end, run_decay, nruns};
+    const GradClip clip = {clip_scale, clip_value};
     const double bytes = (momentum > 0.f ? 20.0 : 12.0) * (double)count + 12.0 * nruns;
     if (momentum == 0.f)
         SSDSEG_LAUNCH_NAMED(ctx, CLIP ? "sgd_clipped_kernel" : "sgd_kernel", bytes, 0.0, (sgd_kernel<SGD_PLAIN, CLIP>), dim3(blocks), dim3(256), 0,
@@ -82,27 +93,13 @@ int sgd_launch(ssdseg_ctx* ctx, float* params, const float* grads, float* veloci
 
 extern "C" int ssdseg_sgd_step(ssdseg_ctx* ctx, float* params, const float* grads, float* velocity, size_t count, float lr, float momentum,
                                int nesterov, float grad_scale, const long long* run_end, const float* run_decay, int nruns) {
-    SSDSEG_ARG(ctx != nullptr, 1);
-    SSDSEG_ARG(params != nullptr, 2);
-    SSDSEG_ARG(grads != nullptr, 3);
-    SSDSEG_ARG(momentum >= 0.f && momentum < 1.f, 7);
-    SSDSEG_ARG(velocity != nullptr || momentum == 0.f, 4);
-    SSDSEG_DECAY_ARGS(run_end, run_decay, nruns, 10, 11, 12);
-    if (count == 0) return 0;
-    return sgd_launch<false>(ctx, params, grads, velocity, count, lr, momentum, nesterov, grad_scale, run_end, run_decay, nruns, GradClip{nullptr, 0.f});
+    return sgd_launch<false>(__func__, ctx, params, grads, velocity, count, lr, momentum, nesterov, grad_scale, run_end, run_decay, nruns,
+                             nullptr, 0.f);
 }
 
 extern "C" int ssdseg_sgd_step_clipped(ssdseg_ctx* ctx, float* params, const float* grads, float* velocity, size_t count, float lr,
                                        float momentum, int nesterov, float grad_scale, const long long* run_end, const float* run_decay,
                                        int nruns, const float* clip_scale, float clip_value) {
-    SSDSEG_ARG(ctx != nullptr, 1);
-    SSDSEG_ARG(params != nullptr, 2);
-    SSDSEG_ARG(grads != nullptr, 3);
-    SSDSEG_ARG(momentum >= 0.f && momentum < 1.f, 7);
-    SSDSEG_ARG(velocity != nullptr || momentum == 0.f, 4);
-    SSDSEG_DECAY_ARGS(run_end, run_decay, nruns, 10, 11, 12);
-    SSDSEG_ARG(clip_value > 0.f, 14);                      // +inf: no clamp; fails for NaN
-    if (count == 0) return 0;
-    return sgd_launch<true>(ctx, params, grads, velocity, count, lr, momentum, nesterov, grad_scale, run_end, run_decay, nruns,
-                            GradClip{clip_scale, clip_value});
+    return sgd_launch<true>(__func__, ctx, params, grads, velocity, count, lr, momentum, nesterov, grad_scale, run_end, run_decay, nruns,
+                            clip_scale, clip_value);
 }

@@ -3,12 +3,12 @@ for a fixed batch size and mode -- the stand-in for Keras' GradientTape and Adam
 Everything stays resident in HBM (288 GB): no recomputation, no activation re-use planning; the launch list is static (no
 Python-side decisions inside a step besides the op order).  The engine owns the parameter bucket, the concat plan, the
 two-stream schedule, the lowering and forward / backward.  `_loss_bind` binds the compiled losses and metrics to it, `_loaders` fills
-its input and target buffers; fit / predict / evaluate are `_fit`.
+its input and target buffers; fit / predict / evaluate are `_fit`.  The optimizer is `_optim.OptimState`, one per parameter set
+(`engine.opt`): its state and every update launch live there, and `optimizer_step` / `adam_step` below only delegate.
 """
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -17,8 +17,8 @@ import numpy as np
 from . import _graph as K
 from . import _hip as H
 from . import layers as L
-from . import optimizers as O
 from ._loss_bind import LossBinding, bind_losses, bind_metrics, launch_metrics  # noqa: F401  (LossBinding: re-exported)
+from ._optim import OptimState
 from ._ops import (ACT_NONE, ACT_RELU, ActBwdOp, ApplyOp, BilinearOp, BNRec, BnOp, ChannelStatsOp, Conv3Op, DecodeNmsOp, DwOp, GapOp,
                    HeadGatherOp, MaskHeadOp, MaxPoolOp, Op, PwOp, ShuffleOp, SoftmaxRowsOp, SplitGatherOp, StemOp, Store, TableShuffleOp,
                    Val, _act_of, _nonneg, pad4)
@@ -77,16 +77,18 @@ class Engine:
             for l, wname, arr in st:
                 owner["index"][(id(l), wname)] = ("state", off, arr.shape)
                 off += arr.size
-            owner["grads"] = owner["adam_m"] = owner["adam_v"] = None
+            owner["grads"] = None
+            owner["opt"] = holder._optim = OptimState(owner, holder)
             holder._engine_params = owner
             for l in self.model.layers:
                 if l.weights:
                     l._engine_sync = (self._pull_layer, self._push_layer)
-        self.P = owner
+        self.P, self.opt = owner, owner["opt"]
         if self.training and owner["grads"] is None:
-            n = owner["n_tr"]
-            owner["grads"] = grad_bucket if grad_bucket is not None else self.ctx.zeros(n)
-            owner["adam_m"], owner["adam_v"] = self.ctx.zeros(n), self.ctx.zeros(n)
+            owner["grads"] = grad_bucket if grad_bucket is not None else self.ctx.zeros(owner["n_tr"])
+            # Adam's two buckets, also under SGD: dropping them there would change the order of device allocations under every
+            # benchmark, which is a change of its own
+            self.opt.slot("m"), self.opt.slot("v")
 
     @staticmethod
     def _phys_shape(wname: str, shape) -> Tuple[int, ...]:
@@ -778,7 +780,7 @@ class Engine:
         return out
 
     def train_step(self, images=None, targets=None, optimizer=None, allreduce=None, world=1):
-        self._not_averaging()
+        self.opt.check_not_averaging()
         if images is not None:
             self.set_input(images)
         if targets is not None:
@@ -791,111 +793,10 @@ class Engine:
         self.optimizer_step(optimizer, grad_scale=1.0 / world)
 
     def optimizer_step(self, o, grad_scale=1.0):
-        """the update of the compiled optimizer `o` (optimizers.Adam / SGD; None: Adam at its defaults here).  A schedule is
-        evaluated at the number of updates already applied -- P["step"] before it is incremented -- in float64; the C call
-        rounds it to float32.  P["lr"] keeps the rate of the last update for fit's history.
-        Clipping and the EMA (optimizers._Optimizer._clip_and_ema) stay on the device: the norm entry leaves its factor in P["clip"],
-        the *_clipped step reads it from there, and the EMA pass follows the step -- all queued, nothing downloaded."""
-        self._not_averaging()
-        if o is None:
-            return self.adam_step(grad_scale=grad_scale)
-        self._restore_optimizer_state()            # before the schedule reads the step counter
-        P = self.P
-        lr = P["lr"] = O.rate_at(o.learning_rate, P.get("step", 0))
-        clip = self._clip_args(o, grad_scale)
-        if o.use_ema and P.get("ema") is None:
-            P["ema"] = self.ctx.empty(P["n_tr"]).copy_from(P["params"])      # the average starts as the weights before the first update
-        if isinstance(o, O.SGD):
-            self.sgd_step(lr=lr, momentum=o.momentum, nesterov=o.nesterov, grad_scale=grad_scale, decay=self._decay_table(o), clip=clip)
-        else:
-            self.adam_step(lr=lr, beta1=o.beta_1, beta2=o.beta_2, eps=o.epsilon, grad_scale=grad_scale, decay=self._decay_table(o), clip=clip)
-        if o.use_ema:
-            self.ctx.call("ssdseg_ema_update", P["ema"], P["params"], C.c_size_t(P["n_tr"]), o.ema_momentum)
-            if o.ema_overwrite_frequency and P["step"] % o.ema_overwrite_frequency == 0:
-                P["params"].copy_from(P["ema"])
-
-    def _not_averaging(self):
-        if self.P.get("averaging"):
-            raise RuntimeError("no training step inside optimizers.averaged_weights: the parameter bucket holds the averaged weights")
-
-    def _clip_args(self, o, grad_scale):
-        """(device pointer to the clip factor or None, clip value) for the *_clipped step entries; None when the optimizer does not
-        clip -- the step then makes the calls it made before there was clipping.  With global_clipnorm the norm entry is queued here:
-        P["clip"] = {norm, factor}, with its partials allocated on first use."""
-        if o.global_clipnorm is None and o.clipvalue is None:
-            return None
-        if o.global_clipnorm is None:
-            return None, o.clipvalue
-        P = self.P
-        n = C.c_size_t(P["n_tr"])
-        if P.get("clip") is None:
-            P["clip"] = self.ctx.zeros(2)
-            P["clip_parts"] = self.ctx.empty(max(self.ctx.lib.ssdseg_grad_norm_parts(P["n_tr"]), 1), np.float64)
-        self.ctx.call("ssdseg_grad_norm", P["grads"], n, grad_scale, o.global_clipnorm, P["clip_parts"], P["clip"])
-        return P["clip"].view(1, (1,)), math.inf
-
-    def _decay_table(self, o):
-        """the optimizer's weight-decay run table over the parameter bucket (optimizers.decay_runs; None without decay): built once
-        per model and (weight_decay, names) from P["index"] in bucket order, uploaded once"""
-        if o.weight_decay == 0.0:
-            return None
-        cache = self.P.setdefault("decay_tables", {})
-        key = (o.weight_decay, o.weight_decay_names)
-        if key not in cache:
-            entries = sorted((off, wname, int(np.prod(shape))) for (_, wname), (which, off, shape) in self.P["index"].items() if which == "params")
-            ends, lams = O.decay_runs([(wname, off, size) for off, wname, size in entries], *key)
-            assert ends.size and ends[-1] == self.P["n_tr"]
-            cache[key] = (self.ctx.array(ends), self.ctx.array(lams), int(ends.size))
-        return cache[key]
-
-    def _restore_optimizer_state(self):
-        restore_optimizer_state(self.model, self.P)
+        self.opt.step_with(o, grad_scale)
 
     def adam_step(self, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, decay=None, clip=None):
-        self._restore_optimizer_state()
-        P = self.P
-        P["step"] = P.get("step", 0) + 1          # shared by every engine (batch size) of the same model
-        if clip is not None:
-            self.ctx.call("ssdseg_adamw_step_clipped", P["params"], P["grads"], P["adam_m"], P["adam_v"], C.c_size_t(P["n_tr"]), lr, beta1, beta2,
-                          eps, P["step"], grad_scale, *(decay or (None, None, 0)), *clip)
-        elif decay is None:
-            self.ctx.call("ssdseg_adam_step", P["params"], P["grads"], P["adam_m"], P["adam_v"], C.c_size_t(P["n_tr"]), lr, beta1, beta2, eps,
-                          P["step"], grad_scale)
-        else:
-            self.ctx.call("ssdseg_adamw_step", P["params"], P["grads"], P["adam_m"], P["adam_v"], C.c_size_t(P["n_tr"]), lr, beta1, beta2, eps,
-                          P["step"], grad_scale, *decay)
-
-    def sgd_step(self, lr=0.01, momentum=0.0, nesterov=False, grad_scale=1.0, decay=None, clip=None):
-        self._restore_optimizer_state()
-        P = self.P
-        P["step"] = P.get("step", 0) + 1
-        if momentum > 0 and P.get("velocity") is None:
-            P["velocity"] = self.ctx.zeros(P["n_tr"])     # allocated on first use: an Adam run never pays for it
-        self.ctx.call("ssdseg_sgd_step" if clip is None else "ssdseg_sgd_step_clipped", P["params"], P["grads"],
-                      P.get("velocity") if momentum > 0 else None, C.c_size_t(P["n_tr"]), lr, momentum, int(bool(nesterov)), grad_scale,
-                      *(decay or (None, None, 0)), *(clip or ()))
-
-
-def restore_optimizer_state(model, P):
-    """state that optimizers.set_state / load_state left on `model`: into the step counter and the state buckets of its parameter
-    set P (the averaged weights, slot `ema`, included)"""
-    pend = model.__dict__.pop("_optimizer_state", None)
-    if pend is None:
-        return
-    ctx = P["params"].ctx
-    P["step"] = pend["step"]
-    names = {id(l): l.name for l in model.layers}
-    flat = {}
-    for (lid, wname), (which, off, shape) in P["index"].items():
-        for slot in O.BUCKETS:
-            arr = pend["arrays"].get(f"{names[lid]}/{wname}:{slot}") if which == "params" else None
-            if arr is not None:
-                flat.setdefault(slot, np.zeros(P["n_tr"], np.float32))[off:off + arr.size] = arr.reshape(-1)
-    for slot, host in flat.items():
-        bucket = O.BUCKETS[slot]
-        if P.get(bucket) is None:
-            P[bucket] = ctx.empty(P["n_tr"])
-        P[bucket].upload(host)
+        self.opt.adam(lr, beta1, beta2, eps, grad_scale, decay, clip)
 
 
 _default_ctx: Optional[H.Context] = None

@@ -165,9 +165,9 @@ def run_fit(model: K.Model, data, epochs=1, validation_data=None, verbose=0) -> 
         logs = {k: v / max(seen, 1) for k, v in sums.items()}
         opt = model._compiled.get("optimizer")
         if seen and opt is not None and callable(getattr(opt, "learning_rate", None)):
-            logs["lr"] = float(np.float32(eng.P["lr"]))      # a scheduled rate: the one of the epoch's last step, as the kernel took it
+            logs["lr"] = float(np.float32(eng.opt.lr))      # a scheduled rate: the one of the epoch's last step, as the kernel took it
         if seen and getattr(opt, "global_clipnorm", None) is not None:
-            logs["grad_norm"] = float(eng.P["clip"].download()[0])      # the pre-clip norm of the epoch's last update: 8 bytes, once per epoch
+            logs["grad_norm"] = float(eng.opt.clip.download()[0])      # the pre-clip norm of the epoch's last update: 8 bytes, once per epoch
         if validation_data is not None:
             vs, vseen = {}, 0
             for x, y in _batches(validation_data):

@@ -10,6 +10,9 @@ Both also take Keras' `global_clipnorm` / `clipvalue` and `use_ema` / `ema_momen
 produced and consumed on the device (ssdseg_grad_norm, then ssdseg_sgd_step_clipped / ssdseg_adamw_step_clipped), the average is
 a pass after the step (ssdseg_ema_update); `_clip_reference` and `_ema_reference` are their specifications, and
 `averaged_weights` / `finalize_variable_values` put the average where predict, evaluate and Model.save see it.
+Everything here works from the graph and NumPy.  The state on the device and the step itself are `_optim.OptimState`; the checkpoint
+and the averaged-weights functions reach it through the model (`model._optim`, set with the model's first engine), so this module
+imports neither that module nor the engine's.
 
 A learning rate is a float or a schedule: a callable `step -> float`, evaluated on the host in float64 with `step` = the number
 of updates already applied (0 for the first), and rounded once to float32 where it is handed to the kernel.
@@ -272,9 +275,6 @@ def _adamw_reference(p, g, m, v, step, lr=1e-3, b1=0.9, b2=0.999, eps=1e-7, grad
 
 
 # ===================================================================================================== checkpoint
-BUCKETS = {"m": "adam_m", "v": "adam_v", "velocity": "velocity", "ema": "ema"}      # state slot -> the engine's bucket
-
-
 def state_slots(opt):
     """the optimizer's slots plus `ema`, the averaged weights, when it keeps them"""
     return tuple(opt.slots) + (("ema",) if opt.use_ema else ())
@@ -295,18 +295,15 @@ def get_state(model):
     pending = model.__dict__.get("_optimizer_state")
     if pending is not None:
         return pending["kind"], pending["step"], {k: a.copy() for k, a in pending["arrays"].items()}
-    P = getattr(model, "_engine_params", None)
+    state = getattr(model, "_optim", None)          # _optim.OptimState, once the model has an engine
     arrays = {}
     for slot in state_slots(opt):
-        buf = P.get(BUCKETS[slot]) if P is not None else None
-        if buf is None and slot == "ema" and P is not None:
-            buf = P["params"]                      # no update yet: the average starts as the weights (Keras initialises it from the variable)
-        flat = buf.download().reshape(-1) if buf is not None else None
+        flat = state.download(slot) if state is not None else None
         for l, wname, off, size in bucket_entries(model):
             shape = l.weights[wname].shape
             initial = np.array(l.weights[wname], np.float32) if slot == "ema" else np.zeros(shape, np.float32)
             arrays[f"{l.name}/{wname}:{slot}"] = flat[off:off + size].reshape(shape).copy() if flat is not None else initial
-    return opt.kind, int(P.get("step", 0)) if P is not None else 0, arrays
+    return opt.kind, int(state.step) if state is not None else 0, arrays
 
 
 def set_state(model, kind: str, step: int, arrays) -> None:
@@ -351,29 +348,26 @@ def load_state(model, path) -> None:
 
 
 # ===================================================================================================== averaged weights
-def _ema_buckets(model):
-    """(P, the EMA bucket) of a model whose optimizer keeps averaged weights; state that `set_state` left is applied first.  Before
-    the first update there is no bucket (None): the average IS the weights then."""
+def _ema_state(model):
+    """the optimizer state (_optim.OptimState) of a model whose optimizer keeps averaged weights, with what `set_state` left applied;
+    None before the model's first engine: the average IS the weights then"""
     opt = _compiled_optimizer(model)
     if not opt.use_ema:
         raise ValueError("the compiled optimizer keeps no averaged weights: build it with use_ema=True")
-    P = getattr(model, "_engine_params", None)
-    if P is None:
+    state = getattr(model, "_optim", None)
+    if state is None:
         if model.__dict__.get("_optimizer_state") is not None:
             raise RuntimeError("the restored averaged weights reach the device with the model's first engine: call predict or train once")
-        return None, None
-    from . import _engine
-    _engine.restore_optimizer_state(model, P)
-    return P, P.get("ema")
+        return None
+    state.restore()
+    return state
 
 
 def finalize_variable_values(model) -> None:
     """Keras' `optimizer.finalize_variable_values`: the weights become the averaged weights, for good"""
-    P, ema = _ema_buckets(model)
-    if ema is not None:
-        if P.get("averaging"):
-            raise RuntimeError("inside averaged_weights the weights are the average already")
-        P["params"].copy_from(ema)
+    state = _ema_state(model)
+    if state is not None:
+        state.finalize()
 
 
 class averaged_weights:
@@ -386,22 +380,11 @@ class averaged_weights:
         self.model = model
 
     def __enter__(self):
-        self.P, ema = _ema_buckets(self.model)
-        if ema is None:
-            self.P = None                          # no update yet: the weights are the average
-            return self.model
-        P = self.P
-        if P.get("averaging"):
-            raise RuntimeError("averaged_weights blocks do not nest")
-        if P.get("ema_backup") is None:
-            P["ema_backup"] = P["params"].ctx.empty(P["n_tr"])
-        P["ema_backup"].copy_from(P["params"])
-        P["params"].copy_from(ema)
-        P["averaging"] = True
+        state = _ema_state(self.model)
+        self.state = state if state is not None and state.swap_in_average() else None      # None: no update yet, the weights are the average
         return self.model
 
     def __exit__(self, *exc):
-        if self.P is not None:
-            self.P["params"].copy_from(self.P["ema_backup"])
-            self.P["averaging"] = False
+        if self.state is not None:
+            self.state.swap_out_average()
         return False

@@ -304,3 +304,18 @@ def test_optimizer_state_file_round_trip(tmp_path):
     Opt.load_state(again, str(tmp_path / "adam.npz"))
     kind, step, arrays = Opt.get_state(again)
     assert (kind, step) == ("adam", 7) and all(np.array_equal(arrays[k], a) for k, a in placed.items())
+
+
+# ------------------------------------------------------------------------------------------------------------ imports
+def test_optimizers_imports_neither_the_engine_nor_the_state_object():
+    """in a fresh interpreter `import ssdseglib.optimizers` succeeds and loads neither ssdseglib._engine nor ssdseglib._optim:
+    descriptions, schedules, specifications and the checkpoint reach the device-side state through the model only"""
+    import subprocess
+    import sys
+    import ssdseglib
+    pkg = os.path.dirname(os.path.dirname(os.path.abspath(ssdseglib.__file__)))
+    code = ("import sys; sys.path.insert(0, sys.argv[1]); import ssdseglib.optimizers; "
+            "print(sorted(m for m in ('ssdseglib._engine', 'ssdseglib._optim') if m in sys.modules))")
+    r = subprocess.run([sys.executable, "-c", code, pkg], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
+    assert r.stdout.decode().strip() == "[]"

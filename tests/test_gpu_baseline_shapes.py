@@ -412,7 +412,7 @@ def test_full_train_step_batch32_480x640_properties(ctx, guards, workload):
 
     def run():
         P["params"].upload(p0); P["state"].upload(s0)
-        P["adam_m"].zero_(); P["adam_v"].zero_(); P["step"] = 0
+        eng.opt.slot("m").zero_(); eng.opt.slot("v").zero_(); eng.opt.step = 0
         step()
         ctx.sync()
         return P["grads"].download(), P["params"].download(), P["state"].download(), eng.losses()

@@ -262,7 +262,7 @@ def test_validation_writes_no_state(ctx, rng):
     assert same(snapshot(ctx, eng), s0), "validation changed params, state, Adam moments or the step counter"
     after_val = step()
     P = eng.P
-    P["params"].upload(s0["p"]); P["state"].upload(s0["s"]); P["adam_m"].upload(s0["m"]); P["adam_v"].upload(s0["v"]); P["step"] = s0["t"]
+    P["params"].upload(s0["p"]); P["state"].upload(s0["s"]); eng.opt.slot("m").upload(s0["m"]); eng.opt.slot("v").upload(s0["v"]); eng.opt.step = s0["t"]
     replay = step()
     assert same(after_val[0], replay[0]) and np.array_equal(after_val[1].view(np.uint32), replay[1].view(np.uint32))
     assert after_val[2].keys() == replay[2].keys() and all(after_val[2][k] == replay[2][k] or np.isnan(replay[2][k]) for k in replay[2])

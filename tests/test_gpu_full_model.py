@@ -247,7 +247,7 @@ def test_detection_branch_on_the_side_stream_is_bit_identical(ctx, rng, monkeypa
     def run(split):
         monkeypatch.setenv("SSDSEG_DET_SIDE", "1" if split else "0")
         P["params"].upload(p0); P["state"].upload(s0)
-        P["adam_m"].zero_(); P["adam_v"].zero_(); P["step"] = 0
+        eng.opt.slot("m").zero_(); eng.opt.slot("v").zero_(); eng.opt.step = 0
         eng.train_step(x, targets, optimizer=model._compiled["optimizer"])
         ctx.sync()
         return P["grads"].download(), P["params"].download(), P["state"].download(), eng.losses()

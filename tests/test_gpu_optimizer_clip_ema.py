@@ -304,7 +304,7 @@ def test_global_clipnorm_through_the_engine(ctx):
     opt = Opt.SGD(momentum=0.9, weight_decay=1e-2, global_clipnorm=CLIPNORM)
     model, eng, p0 = trained_once(ctx, 1993, opt)
     P = eng.P
-    g0, got_p, got_v, clip = P["grads"].download(), P["params"].download(), P["velocity"].download(), P["clip"].download()
+    g0, got_p, got_v, clip = P["grads"].download(), P["params"].download(), eng.opt.slots["velocity"].download(), eng.opt.clip.download()
     norm64, factor64 = Opt._clip_reference(g0, 1.0, f32(CLIPNORM))
     assert norm64 > CLIPNORM and factor64 < 1, "the clip is not live"
     assert ulps(clip[0], norm64) <= 1 and ulps(clip[1], factor64) <= 1, (clip, norm64, factor64)
@@ -324,7 +324,7 @@ def test_global_clipnorm_through_the_engine(ctx):
     # the mean gradient of two ranks that hold the same gradient
     _, eng2, p0_2 = trained_once(ctx, 1993, Opt.SGD(momentum=0.9, weight_decay=1e-2, global_clipnorm=CLIPNORM), world=2)
     assert np.array_equal(bits(p0_2), bits(p0)) and np.array_equal(bits(eng2.P["grads"].download()), bits(g0)), "the twin is no twin"
-    half = eng2.P["clip"].download()
+    half = eng2.opt.clip.download()
     assert ulps(half[0], norm64 / 2) <= 1 and ulps(half[0], np.float32(0.5) * clip[0]) <= 1, (half, clip)
     assert ulps(half[1], Opt._clip_reference(g0, 0.5, f32(CLIPNORM))[1]) <= 1
 
@@ -335,8 +335,8 @@ def test_a_clip_that_never_bites_is_the_run_without_it(ctx):
     plain = trained_once(ctx, 7, Opt.SGD(momentum=0.9, weight_decay=1e-2), steps=2)[1]
     huge = trained_once(ctx, 7, Opt.SGD(momentum=0.9, weight_decay=1e-2, global_clipnorm=1e30), steps=2)[1]
     a, b = run_snapshot(ctx, plain, ("velocity",)), run_snapshot(ctx, huge, ("velocity",))
-    assert a["t"] == b["t"] == 2 and plain.P.get("clip") is None
-    clip = huge.P["clip"].download()
+    assert a["t"] == b["t"] == 2 and plain.opt.clip is None
+    clip = huge.opt.clip.download()
     assert clip[0] > CLIPNORM and clip[1] == 1.0
     for key in ("p", "s", "velocity"):
         assert np.array_equal(bits(a[key]), bits(b[key])), f"{key} differs from the run without global_clipnorm"
@@ -368,8 +368,8 @@ def test_clipvalue_through_the_engine(ctx):
     opt = Opt.Adam(learning_rate=1e-3, weight_decay=1e-2, clipvalue=value)
     model, eng, p0 = trained_once(ctx, 1993, opt)
     P = eng.P
-    assert P.get("clip") is None
-    g0, got_p, got_m, got_v = (P[k].download() for k in ("grads", "params", "adam_m", "adam_v"))
+    assert eng.opt.clip is None
+    g0, got_p, got_m, got_v = (b.download() for b in (P["grads"], P["params"], eng.opt.slots["m"], eng.opt.slots["v"]))
     c = f32(value)
     over = np.abs(g0) > c
     assert 0.01 < over.mean() < 0.99, over.mean()
@@ -400,7 +400,7 @@ def test_ema_through_the_engine(ctx, rng, tmp_path):
     compile_with(model, opt)
     data = batches(rng, boxes, 3)
     eng = E.engine_for(model, 3, True)
-    P = eng.P
+    P, S = eng.P, eng.opt
     p0 = P["params"].download()
     before = Opt.get_state(model)[2]
     for l, w, off, size in Opt.bucket_entries(model):
@@ -409,12 +409,12 @@ def test_ema_through_the_engine(ctx, rng, tmp_path):
     for k, (x, targets) in enumerate(data):
         eng.train_step(x, targets, optimizer=opt)
         ctx.sync()
-        p_new, ema = P["params"].download(), P["ema"].download()
+        p_new, ema = P["params"].download(), S.slots["ema"].download()
         want, bound = ema_bound(ema_prev, p_new, f32(0.5))
         print(f"\nupdate {k + 1}: " + assert_within("ema", ema, want, bound))
         assert not np.array_equal(ema, p_new) and not np.array_equal(ema, ema_prev)
         ema_prev = ema
-    raw, ema = P["params"].download(), P["ema"].download()
+    raw, ema = P["params"].download(), S.slots["ema"].download()
     state = P["state"].download()
     with Opt.averaged_weights(model) as m:
         assert m is model and np.array_equal(bits(P["params"].download()), bits(ema)), "inside, the bucket holds the EMA"
@@ -431,14 +431,14 @@ def test_ema_through_the_engine(ctx, rng, tmp_path):
     with pytest.raises(ZeroDivisionError):
         with Opt.averaged_weights(model):
             1 / 0
-    assert np.array_equal(bits(P["params"].download()), bits(raw)) and not P["averaging"], "the raw parameters are not back after an exception"
-    assert np.array_equal(bits(P["state"].download()), bits(state)) and np.array_equal(bits(P["ema"].download()), bits(ema))
-    assert P["step"] == 3
+    assert np.array_equal(bits(P["params"].download()), bits(raw)) and not S.averaging, "the raw parameters are not back after an exception"
+    assert np.array_equal(bits(P["state"].download()), bits(state)) and np.array_equal(bits(S.slots["ema"].download()), bits(ema))
+    assert S.step == 3
     eng.train_step(*data[0], optimizer=opt)              # training goes on afterwards
     ctx.sync()
-    assert P["step"] == 4
+    assert S.step == 4
     Opt.finalize_variable_values(model)
-    assert np.array_equal(bits(P["params"].download()), bits(P["ema"].download()))
+    assert np.array_equal(bits(P["params"].download()), bits(S.slots["ema"].download()))
 
 
 def test_ema_overwrite_frequency(ctx, rng):
@@ -453,7 +453,7 @@ def test_ema_overwrite_frequency(ctx, rng):
     for x, targets in batches(rng, boxes, 3):
         eng.train_step(x, targets, optimizer=opt)
         ctx.sync()
-        same.append(bool(np.array_equal(bits(eng.P["params"].download()), bits(eng.P["ema"].download()))))
+        same.append(bool(np.array_equal(bits(eng.P["params"].download()), bits(eng.opt.slots["ema"].download()))))
     assert same == [False, True, False]
 
 
@@ -473,7 +473,7 @@ def test_resume_with_clipping_and_ema(ctx, rng, kind, tmp_path):
         return Opt.Adam(learning_rate=sched, weight_decay=1e-2, **extra) if kind == "adam" else \
             Opt.SGD(learning_rate=sched, momentum=0.9, nesterov=True, weight_decay=1e-2, **extra)
 
-    slots = (("adam_m", "adam_v") if kind == "adam" else ("velocity",)) + ("ema", "clip")
+    slots = (("m", "v") if kind == "adam" else ("velocity",)) + ("ema", "clip")
 
     def fresh():
         boxes, _, model = build()

@@ -334,9 +334,9 @@ def test_one_model_step_with_nesterov_sgd_and_weight_decay(ctx, rng):
     p0 = eng.P["params"].download()
     eng.train_step(x, targets, optimizer=opt)
     ctx.sync()
-    P = eng.P
-    assert P["step"] == 1 and P["lr"] == 0.01
-    g0, got_p, got_v = P["grads"].download(), P["params"].download(), P["velocity"].download()
+    P, S = eng.P, eng.opt
+    assert S.step == 1 and S.lr == 0.01
+    g0, got_p, got_v = P["grads"].download(), P["params"].download(), S.slots["velocity"].download()
     assert np.abs(g0).max() > 0
     lr, mu = f32(0.01), f32(0.9)
     ends, lams = layer_table(model, 1e-2, ("kernel", "pointwise_kernel"))
@@ -347,7 +347,7 @@ def test_one_model_step_with_nesterov_sgd_and_weight_decay(ctx, rng):
     assert np.allclose(sp, wp, rtol=1e-12, atol=0)
     print("\nmodel step, Nesterov SGD + decay: " + assert_within("p", got_p, sp, bp) + "; " + assert_within("v", got_v, sv, bv))
     # the engine's cached table is the merged form of the same thing
-    (d_ends, d_lams, nruns), = P["decay_tables"].values()
+    (d_ends, d_lams, nruns), = S.decay_tables.values()
     assert nruns < ends.size and np.array_equal(Opt.expand_runs(d_ends.download(), d_lams.download(), p0.size), lam)
     # control
     ends_c, lams_c = layer_table(model, 1e-2, ("kernel", "pointwise_kernel", "gamma"))
@@ -375,17 +375,17 @@ def test_schedules_reach_the_kernel(ctx, rng, kind):
     assert hist.history["lr"] == [f32(1e-2), f32(1e-3)]
     loss_keys = set(hist.history) - {"lr"}
     eng = E.engine_for(model, 3, True)
-    P = eng.P
-    assert P["step"] == 2
-    P["step"] = 0                                   # the schedule again from its start, on the state the two epochs left
+    P, S = eng.P, eng.opt
+    assert S.step == 2
+    S.step = 0                                      # the schedule again from its start, on the state the two epochs left
     b1, b2, eps = f32(0.9), f32(0.999), f32(1e-7)
-    slots = ("adam_m", "adam_v") if kind == "adam" else ("velocity",)
+    slots = ("m", "v") if kind == "adam" else ("velocity",)
     for k, (x, targets) in enumerate(data):
         ctx.sync()
-        p0, s0 = P["params"].download(), [P[s].download() for s in slots]
+        p0, s0 = P["params"].download(), [S.slots[s].download() for s in slots]
         eng.train_step(x, targets, optimizer=opt)
         ctx.sync()
-        assert P["step"] == k + 1 and P["lr"] == values[k]
+        assert S.step == k + 1 and S.lr == values[k]
         g0, got = P["grads"].download(), P["params"].download()
 
         def at(rate):
@@ -413,7 +413,7 @@ def test_schedules_reach_the_kernel(ctx, rng, kind):
 def run_snapshot(ctx, eng, slots):
     ctx.sync()
     P = eng.P
-    return {"p": P["params"].download(), "s": P["state"].download(), "t": P["step"], **{s: P[s].download() for s in slots}}
+    return {"p": P["params"].download(), "s": P["state"].download(), "t": eng.opt.step, **{s: (eng.opt.clip if s == "clip" else eng.opt.slots[s]).download() for s in slots}}
 
 
 @pytest.mark.parametrize("kind", ["adam", "sgd"])
@@ -429,7 +429,7 @@ def test_resume_from_weights_and_optimizer_state(ctx, rng, kind, tmp_path):
         return Opt.Adam(learning_rate=sched, weight_decay=1e-2) if kind == "adam" else \
             Opt.SGD(learning_rate=sched, momentum=0.9, nesterov=True, weight_decay=1e-2)
 
-    slots = ("adam_m", "adam_v") if kind == "adam" else ("velocity",)
+    slots = ("m", "v") if kind == "adam" else ("velocity",)
 
     def fresh():
         boxes, _, model = build()

@@ -59,7 +59,7 @@ def compile_model(model):
 def snapshot(ctx, eng):
     ctx.sync()
     P = eng.P
-    return dict(p=P["params"].download(), s=P["state"].download(), m=P["adam_m"].download(), v=P["adam_v"].download(), t=P.get("step", 0))
+    return dict(p=P["params"].download(), s=P["state"].download(), m=eng.opt.slots["m"].download(), v=eng.opt.slots["v"].download(), t=eng.opt.step)
 
 
 def oracle_from_device(model, eng):
@@ -289,7 +289,7 @@ def test_training_steps_teacher_forced(ctx, rng, case):
         x = rng.integers(0, 256, (1,) + SHAPE).astype(np.float32)
         counts = chk.step(eng1, x, targets_for(1))
         assert -1.0 in chk.last_errs.values(), "the batch-1 step should meet the one-value BatchNorm of the image-pooling branch"
-        assert eng.P["step"] == 3
+        assert eng.opt.step == 3
         assert 1 in counts and any(c > 1 for c in counts), counts        # both branches of the Bessel correction taken
         # inference forward with the moving statistics the three steps left
         inf = E.Engine(model, 1, training=False, ctx=ctx)
