@@ -1,6 +1,7 @@
 """What a `_graph.Model` is lowered to: tensor bookkeeping (`Store`, `BNRec`, `Val`) and one `Op` class per fused HIP launch family.
-`_engine.Engine` builds the static launch list out of these; an op's `fwd` / `bwd` body is its part of that list -- the calls
-into include/ssdseg.h, in order.
+`_lowering.Lowering` builds the static launch list out of these and sets what an op or a store cannot know by itself (every such
+attribute is declared here, with its default); `_engine.Engine` runs the list.  An op's `fwd` / `bwd` body is its part of that
+list -- the calls into include/ssdseg.h, in order.
   * conv -> BatchNormalization(train) -> ReLU6 is never three passes: the conv kernel writes the RAW tensor once
     plus per-block (sum, sumsq); `bn_finalize` makes per-channel (scale, shift); every consumer applies
     act(scale*y+shift) while loading (`Val` below is that lazy view).  Backward mirrors it: one reduction pass per
@@ -56,6 +57,13 @@ class Store:
         self.split_parent = False  # channel Split views write disjoint ranges of this gradient: zero it, then everyone accumulates
         self.stats: Optional[H.DeviceBuffer] = None   # per-block (sum, sumsq) partials from the producing conv
         self.nparts = 0
+        # set by the lowering (`_lowering.Lowering`), None where it does not apply
+        self.producer: Optional["Op"] = None   # the op that writes this store: BatchNormalization / ReLU re-point its `out_val`
+        self.slice_scale = None    # a concat slice's range of its parent's wide_scale: the BatchNorm behind it writes its scale there
+        self.slice_shift = None    # ... and its shift
+        self.wide_scale = None     # a channel concat's per-channel scale over all its inputs (ones where an input has none)
+        self.wide_shift = None     # ... and shift (zeros)
+        self.logical_parts = None  # a channel concat's [(physical channel offset, logical width)] per input (TableShuffleOp)
 
     def slice(self, coff: int, c: int, name: str) -> "Store":
         assert coff + c <= self.c
@@ -133,7 +141,22 @@ class BNRec:
 
 
 class Val:
-    """Lowered value of a symbolic tensor: a = act(scale * store + shift) (scale None -> act(store))."""
+    """Lowered value of a symbolic tensor: a = act(scale * store + shift) (scale None -> act(store)).
+
+    `meta` carries what one lowering rule leaves for a later one (`_lowering.Lowering`, by rule) or for `_loss_bind`; its keys:
+      rescale            (scale, offset) of a Rescaling: set by _rescaling, read by _conv (the stem takes it)
+      decode             the DecodeBoxesCentroidsOffsets layer: set by _decode, read by _nms
+      suppress_with      the mask probabilities' store: set by _suppression, read by _nms
+      lazy_up, src       an UpSampling2D that only a Softmax reads -- its size and its input Val: set by _upsampling, read by _softmax
+      materialised_act   activation already applied to the stored values: set by _upsampling, read by _concat
+      mask_head          the MaskHeadOp of the mask output: set by _softmax, read by _loss_bind
+      logits             the pre-softmax store of the label output: set by _softmax, read by _loss_bind
+      nms                the NonMaximumSuppression layer: set by _nms, read by _fit
+      reshaped           target shape of an SSD head's Reshape: set by _reshape, read by _concat (the anchor-axis concat)
+      head_concat        the (B, anchors, 4) concat of the heads: set by _concat, read by _softmax and _loss_bind
+      shuffle_groups, shuffle_src, shuffle_permuted   the channel shuffle in progress (Reshape, Permute, Reshape): set by _reshape and
+                         _permute, read by _permute and _reshape
+      nonneg             stored values known to be >= 0: set by _maxpool, _split and _reshape, read by `_nonneg` (_concat)"""
 
     def __init__(self, store: Store, scale=None, shift=None, act=ACT_NONE, bn: Optional[BNRec] = None, **meta):
         self.store, self.scale, self.shift, self.act, self.bn = store, scale, shift, act, bn
@@ -154,7 +177,7 @@ class Val:
 # ====================================================================================================== ops
 class Op:
     name = ""
-    reach = frozenset()      # names of the model outputs that depend on this op (set by Engine._emit)
+    reach = frozenset()      # names of the model outputs that depend on this op (set when it is emitted: Lowering.emit, Engine._emit)
 
     def fwd(self):
         pass
@@ -290,19 +313,9 @@ class Conv3Op(Op):
             H._check(eng.ctx.lib.ssdseg_conv3x3_saved_floats(s.n, s.h, s.w, s.c, out.c, C.byref(need)), "ssdseg_conv3x3_saved_floats")
             if need.value > 0:
                 self.xsaved = eng.ctx.zeros(need.value)       # (the border stays zero for the life of the buffer)
-        # The input of the DeepLabV3+ decoder conv is Concatenate(up-sampled ASPP output, backbone branch) (blocks.py:104-113).  The
-        # up-sampling writes final (already activated) values into channels [0, c) of the concat buffer, which the saved-input
-        # forward then copies into the zero-bordered buffer.  Nothing else reads those channels of the plain concat buffer, so the
-        # up-sampling writes them into the bordered buffer directly and the copy shrinks to the other branch's channels.
+        # the first channels of the input that an up-sampling op already writes into `xsaved` itself (set by the lowering together
+        # with that op's `padded_out`, Lowering._upsampling_into_saved_input): the saved-input forward copies only the rest
         self.saved_from = 0
-        if self.xsaved is not None and s.ld == s.c:
-            up = [op for op in eng.ops if isinstance(op, BilinearOp) and op.out.parent is s and op.out.coff == 0 and op.out.ld == s.c
-                  and op.out.h == s.h and op.out.w == s.w]
-            users = [op for op in eng.ops if any((getattr(v, "store", v) is s) for v in vars(op).values())]
-            sole = len(eng.cons.get(id(layer.inbound[0]), [])) == 1 and id(layer.inbound[0]) not in {id(t) for t in eng.model.outputs}
-            if len(up) == 1 and not users and sole:
-                up[0].padded_out = (self.xsaved, s.c)
-                self.saved_from = up[0].out.c
 
     def fwd(self):
         s = self.inp.store
@@ -398,7 +411,8 @@ class ApplyOp(Op):
         self.e.ctx.call("ssdseg_bn_apply", a.view(), a.store.ld, b.view() if b is not None else None, b.store.ld if b is not None else 0,
                         o.buf, o.ld, o.m, o.c)
 
-    alias_a = False   # Add: `a` (a projection's BN output consumed only here) shares this op's output-gradient buffer
+    # set by the lowering for an Add whose `a` (a projection's BN output) is consumed only here: it shares this op's output-gradient buffer
+    alias_a = False
 
     def bwd(self):
         o = self.out
@@ -544,7 +558,7 @@ class BilinearOp(Op):
         self.e, self.inp, self.out, self.fy, self.fx, self.name = eng, inp, out, fy, fx, name
 
     # set by a Conv3Op that keeps a zero-bordered copy of its (concatenated) input: (buffer, row stride in floats) -- this op's
-    # output then goes straight into the interior of that copy and the plain concat slice is not written (Conv3Op.__init__)
+    # output then goes straight into the interior of that copy and the plain concat slice is not written (set by the lowering)
     padded_out = None
 
     def fwd(self):
