@@ -76,9 +76,7 @@ class _EvalStager:
     def load(self, batch):
         """the batch through its loader (pixels -> the engine's input, ground truth -> ld.gt / ld.cnt) -> (ld, its class indices [b][hw])"""
         b, ins = self.eng.batch, self.eng.input_store
-        if (getattr(batch, "crop_windows", None) is not None or getattr(batch, "mosaic", None) is not None
-                or getattr(batch, "rgb_draws", None) is not None
-                or (batch.flip is not None and np.any(batch.flip))):      # (the class indices returned below are as the files hold them)
+        if batch.augmented_by():      # (the class indices returned below are as the files hold them)
             raise ValueError("evaluate_on_device: the batch carries crop windows, a mosaic, colour draws or flip flags; a test set is not augmented")
         ld = loader_for(self.eng, batch)
         ld.stage(batch)

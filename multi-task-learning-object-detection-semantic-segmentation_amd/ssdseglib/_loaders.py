@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _hip as H
+from ._batches import GMAX, pad_ground_truth
 
 
 def batch_size(x) -> int:
@@ -21,15 +22,10 @@ def batch_size(x) -> int:
 
 
 def _pad_ground_truth(ground_truth, b, gmax):
-    """per-image (k_i, 5) rows -> gt (b, gmax, 5) float32, zero-padded, and cnt (b,) int32"""
+    """the b per-image (k_i, 5) rows of a compact batch -> gt (b, gmax, 5) float32, zero-padded, and cnt (b,) int32"""
     if max(g.shape[0] for g in ground_truth) > gmax:
         raise ValueError(f"more than {gmax} ground-truth boxes in one image")
-    gt = np.zeros((b, gmax, 5), np.float32)
-    cnt = np.zeros(b, np.int32)
-    for i, g in enumerate(ground_truth):
-        gt[i, :g.shape[0]] = g
-        cnt[i] = g.shape[0]
-    return gt, cnt
+    return pad_ground_truth(ground_truth, gmax)
 
 
 class _DenseLoader:
@@ -86,8 +82,7 @@ class _DenseLoader:
 
 def _encoder_anchors(ctx, encoder, det, mask_op):
     """the encoder's default boxes on the device, after checking its anchor and class counts against the model's heads"""
-    corners = np.stack([encoder.xmin_boxes_default, encoder.ymin_boxes_default, encoder.xmax_boxes_default, encoder.ymax_boxes_default], axis=1)
-    anchors = ctx.array(corners.astype(np.float32))
+    anchors = ctx.array(encoder._corners())
     if det is not None and anchors.shape[0] != det.y_boxes.shape[1]:
         raise ValueError(f"encoder has {anchors.shape[0]} default boxes, the model's heads {det.y_boxes.shape[1]}")
     # ssdseg_encode_targets writes (batch, anchors, encoder.num_classes) floats into the labels target and the mask is
@@ -113,29 +108,22 @@ class _CropStage:
         self.gt = ctx.empty((b, gmax, 5))
         self.cnt = ctx.empty(b, np.int32)
 
-    def run(self, src_img, src_midx, src_gt, src_cnt, n_src, index, windows, fill, flip_host):
-        """index: the host int32 list of a resident batch or None (n -> n); flip_host: host uint8 flags to hand on to self.flip, or
-        None.  src_midx / src_gt may be None (a model without that head)."""
+    def run(self, src_img, src_midx, src_gt, src_cnt, n_src, index, step, flip_host):
+        """step: the batch's `geometric()`, ("crop", windows, fill) or ("mosaic", mosaic, fill); index: the host int32 list of a
+        resident batch (its pool slots) or None (n -> n); flip_host: host uint8 flags to hand on to self.flip, or None.  src_midx /
+        src_gt may be None (a model without that head)."""
+        kind, what, fill = step
         fill = fill if fill is not None else (0, 0, 0, 0)
-        win = windows.ctypes.data_as(C.POINTER(C.c_float))
-        self.ctx.call("ssdseg_crop_inputs", src_img, src_midx, n_src, None if index is None else index.ctypes.data, win,
-                      (C.c_uint8 * 3)(*fill[:3]), int(fill[3]), None if flip_host is None else flip_host.ctypes.data, self.flip, self.img,
-                      self.midx if src_midx is not None else None, self.b, self.h, self.w)
-        if src_gt is not None:
-            self.ctx.call("ssdseg_crop_gt", src_gt, src_cnt, n_src, None if index is None else index.ctypes.data, win, self.gt, self.cnt,
-                          self.b, self.gmax, self.h, self.w)
-
-    def run_mosaic(self, src_img, src_midx, src_gt, src_cnt, n_src, mosaic, sources, fill, flip_host):
-        """sources: host int32 (b, 4), the source sample of every tile (a compact batch: mosaic.index4 itself, the positions; a resident
-        batch: the pool slots at those positions); the rest as run()"""
-        fill = fill if fill is not None else (0, 0, 0, 0)
-        sources = np.ascontiguousarray(sources, np.int32)
-        lists = (sources.ctypes.data, mosaic.split.ctypes.data, mosaic.windows.ctypes.data_as(C.POINTER(C.c_float)))
-        self.ctx.call("ssdseg_mosaic_inputs", src_img, src_midx, n_src, *lists, (C.c_uint8 * 3)(*fill[:3]), int(fill[3]),
+        if kind == "mosaic":        # the source sample of every tile: the positions within the batch, or the pool slots at those positions
+            sources = np.ascontiguousarray(what.index4 if index is None else index[what.index4], np.int32)
+            lists = (sources.ctypes.data, what.split.ctypes.data, what.windows.ctypes.data_as(C.POINTER(C.c_float)))
+        else:
+            lists = (None if index is None else index.ctypes.data, what.ctypes.data_as(C.POINTER(C.c_float)))
+        self.ctx.call(f"ssdseg_{kind}_inputs", src_img, src_midx, n_src, *lists, (C.c_uint8 * 3)(*fill[:3]), int(fill[3]),
                       None if flip_host is None else flip_host.ctypes.data, self.flip, self.img, self.midx if src_midx is not None else None,
                       self.b, self.h, self.w)
         if src_gt is not None:
-            self.ctx.call("ssdseg_mosaic_gt", src_gt, src_cnt, n_src, *lists, self.gt, self.cnt, self.b, self.gmax, self.h, self.w)
+            self.ctx.call(f"ssdseg_{kind}_gt", src_gt, src_cnt, n_src, *lists, self.gt, self.cnt, self.b, self.gmax, self.h, self.w)
 
 
 class _EncodingLoader:
@@ -143,7 +131,7 @@ class _EncodingLoader:
     loss), the encoder's anchors, the gt / cnt / means buffers, the crop stage and the compact-path calls.  Without an encoder
     (an inference engine: evaluate) there are no targets: only the image is filled and the ground-truth rows are put into gt / cnt."""
 
-    GMAX = 64       # ground-truth rows per image the encode kernel holds in LDS (boxes.hip)
+    GMAX = GMAX     # ground-truth rows per image the encode kernel holds in LDS (boxes.hip): the resident dataset's pools have as many
 
     def __init__(self, eng, encoder):
         self.eng, self.ctx, self.enc = eng, eng.ctx, encoder
@@ -156,11 +144,18 @@ class _EncodingLoader:
         self.staged = None
         self.crop = None
 
-    def _crop_stage(self) -> _CropStage:
+    def _geometric(self, img, midx, gt, cnt, n_src, index, step, flip_host):
+        """the batch's geometric step (`geometric()`: crop, mosaic or None), uint8 -> uint8 into a second compact batch on the device
+        (the crop stage, allocated on first use), from these source buffers or pools of n_src samples; index, flip_host: as
+        _CropStage.run.  -> the compact device buffers (img, midx, gt, cnt) to expand: the stage's, or the sources without a step"""
+        if step is None:
+            return img, midx, gt, cnt
         if self.crop is None:
             ins = self.eng.input_store
             self.crop = _CropStage(self.ctx, self.eng.batch, ins.h, ins.w, self.GMAX)
-        return self.crop
+        crop = self.crop
+        crop.run(img, midx if self.mask_op is not None else None, gt if self.det is not None else None, cnt, n_src, index, step, flip_host)
+        return crop.img, crop.midx, crop.gt, crop.cnt
 
     def _encode(self, gt, cnt) -> None:
         self.ctx.call("ssdseg_encode_targets", self.anchors, self.anchors.shape[0], gt, cnt, self.eng.batch, self.GMAX, self.enc.num_classes,
@@ -200,7 +195,7 @@ class _CompactLoader(_EncodingLoader):
         self.img = ctx.empty((b, ins.h, ins.w, 3), np.uint8)
         self.midx = ctx.empty((b, ins.h, ins.w), np.uint8)
         self.flip = ctx.empty(b, np.uint8)
-        self.draws = self.windows = self.fill = self.mosaic = self._keep = None
+        self.batch = self._keep = None      # the staged batch (its draws and geometric step are read in consume) and its host arrays
 
     def stage(self, cb, y=None, ahead=False) -> bool:
         b, ins = self.eng.batch, self.eng.input_store
@@ -213,31 +208,18 @@ class _CompactLoader(_EncodingLoader):
         for dst, src in pairs:
             self.ctx.upload_async(dst, src, after_fence=True)
         self._keep = [src for _, src in pairs]
-        self.draws = getattr(cb, "rgb_draws", None)
-        self.windows, self.fill = getattr(cb, "crop_windows", None), getattr(cb, "crop_fill", None)
-        self.mosaic = getattr(cb, "mosaic", None)
-        if self.mosaic is not None:
-            self.fill = getattr(cb, "mosaic_fill", None)
-        self.staged = bool(flip.any())
+        self.batch, self.staged = cb, bool(flip.any())
         return True
 
     def consume(self) -> None:
         assert self.staged is not None
-        ctx, b = self.ctx, self.eng.batch
+        ctx, cb = self.ctx, self.batch
         ctx.upload_join()
         flip = self.flip if self.staged else None
-        img, midx, gt, cnt = self.img, self.midx, self.gt, self.cnt
-        if self.windows is not None or self.mosaic is not None:     # first: uint8 -> uint8 into a second compact batch on the device
-            crop = self._crop_stage()
-            src = (img, midx if self.mask_op is not None else None, gt if self.det is not None else None, cnt, b)
-            if self.mosaic is not None:
-                crop.run_mosaic(*src, self.mosaic, self.mosaic.index4, self.fill, None)
-            else:
-                crop.run(*src, None, self.windows, self.fill, None)
-            img, midx, gt, cnt = crop.img, crop.midx, crop.gt, crop.cnt
-        self._expand_compact(img, midx, gt, cnt, flip, self.draws)
+        compact = self._geometric(self.img, self.midx, self.gt, self.cnt, self.eng.batch, None, cb.geometric(), None)
+        self._expand_compact(*compact, flip, cb.rgb_draws)
         ctx.upload_fence()                          # from here on the compact staging buffers may be overwritten
-        self.staged = self.draws = self.windows = self.fill = self.mosaic = None
+        self.staged = self.batch = None
 
 
 class _ResidentLoader(_EncodingLoader):
@@ -255,7 +237,7 @@ class _ResidentLoader(_EncodingLoader):
         b, ins, ds = self.eng.batch, self.eng.input_store, rb.dataset
         if len(rb) != b or (ds.height, ds.width) != (ins.h, ins.w):
             raise ValueError(f"resident batch of {len(rb)} samples of {ds.height}x{ds.width} for an engine of batch {b}, {ins.h}x{ins.w}")
-        if ds.ctx is not self.ctx or ds.GMAX != self.GMAX:
+        if ds.ctx is not self.ctx:
             raise ValueError("resident dataset lives on another context than the model's engine")
         self.staged = rb
         return True
@@ -265,16 +247,11 @@ class _ResidentLoader(_EncodingLoader):
         rb, ctx, b, ins, mask_op = self.staged, self.ctx, self.eng.batch, self.eng.input_store, self.mask_op
         ds = rb.dataset
         self.staged = None
-        mosaic = getattr(rb, "mosaic", None)
-        if getattr(rb, "crop_windows", None) is not None or mosaic is not None:
-            crop = self._crop_stage()
+        step = rb.geometric()
+        if step is not None:
             flip_host = rb.flip if rb.flip is not None and rb.flip.any() else None
-            src = (ds.images, ds.masks if mask_op is not None else None, ds.gt if self.det is not None else None, ds.cnt, ds.num_samples)
-            if mosaic is not None:
-                crop.run_mosaic(*src, mosaic, rb.index[mosaic.index4], rb.mosaic_fill, flip_host)
-            else:
-                crop.run(*src, rb.index, rb.crop_windows, rb.crop_fill, flip_host)
-            self._expand_compact(crop.img, crop.midx, crop.gt, crop.cnt, crop.flip if flip_host is not None else None, rb.rgb_draws)
+            compact = self._geometric(ds.images, ds.masks, ds.gt, ds.cnt, ds.num_samples, rb.index, step, flip_host)
+            self._expand_compact(*compact, self.crop.flip if flip_host is not None else None, rb.rgb_draws)
             return
         index = rb.index.ctypes.data
         flip = rb.flip.ctypes.data if rb.flip is not None and rb.flip.any() else None

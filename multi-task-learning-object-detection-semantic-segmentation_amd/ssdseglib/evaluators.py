@@ -113,19 +113,19 @@ def _nms_layer(model_inference):
     raise ValueError("evaluate_on_device needs a model from get_model_for_inference (no NMS output in this one)")
 
 
+_NOT_PLAIN = {"rgb_draws": "the batch carries colour-augmentation draws",
+              "crop_windows": "the batch carries crop windows; a test set is not augmented",
+              "mosaic": "the batch carries a mosaic; a test set is not augmented",
+              "flip": "the batch has mirrored samples (flip flags set)"}
+
+
 def _check_plain(batch) -> None:
     """evaluation is on the files as they are: no mirrored sample, no colour draws, no crop windows, no mosaic"""
     kind = type(batch).__name__
     if kind not in ("CompactBatch", "ResidentBatch"):
         raise ValueError(f"evaluate_on_device takes CompactBatch / ResidentBatch objects or a ResidentDataset, got {kind}")
-    if getattr(batch, "rgb_draws", None) is not None:
-        raise ValueError("evaluate_on_device: the batch carries colour-augmentation draws")
-    if getattr(batch, "crop_windows", None) is not None:
-        raise ValueError("evaluate_on_device: the batch carries crop windows; a test set is not augmented")
-    if getattr(batch, "mosaic", None) is not None:
-        raise ValueError("evaluate_on_device: the batch carries a mosaic; a test set is not augmented")
-    if batch.flip is not None and np.any(batch.flip):
-        raise ValueError("evaluate_on_device: the batch has mirrored samples (flip flags set)")
+    for carried in batch.augmented_by():
+        raise ValueError("evaluate_on_device: " + _NOT_PLAIN[carried])
 
 
 def _plain_batches(data):

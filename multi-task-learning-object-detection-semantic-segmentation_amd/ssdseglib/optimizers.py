@@ -5,7 +5,7 @@ epsilon 1e-7); `SGD` for `tf.keras.optimizers.SGD`, the optimizer of the recipes
 decay 5e-4, stepped rate; DeepLabV3+: momentum and the "poly" rate; MobileNetV2: decay on the convolution kernels only).  Both
 take Keras 2.13's decoupled `weight_decay`, applied to the weights named in `weight_decay_names`.  The updates themselves are
 the fused HIP kernels ssdseg_adam_step / ssdseg_adamw_step / ssdseg_sgd_step over the flat parameter bucket (include/ssdseg.h);
-`_sgd_reference` and `_adamw_reference` below are their specification, as `datacoder._mosaic_resample` is the mosaic kernel's.
+`_sgd_reference` and `_adamw_reference` below are their specification, as `_augment_spec._mosaic_resample` is the mosaic kernel's.
 Both also take Keras' `global_clipnorm` / `clipvalue` and `use_ema` / `ema_momentum` / `ema_overwrite_frequency`: the clip factor is
 produced and consumed on the device (ssdseg_grad_norm, then ssdseg_sgd_step_clipped / ssdseg_adamw_step_clipped), the average is
 a pass after the step (ssdseg_ema_update); `_clip_reference` and `_ema_reference` are their specifications, and
