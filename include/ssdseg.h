@@ -370,6 +370,29 @@ int ssdseg_mask_head_bwd_bootstrap(ssdseg_ctx* ctx, const float* logits, int n, 
  * loss [n] */
 int ssdseg_bootstrap_ce_loss(ssdseg_ctx* ctx, const float* y_true, const float* p, int n, int hw, int c,
                              const float* class_weights_host, int keep, float* loss);
+/* Void pixels.  A pixel is LABELLED iff any component of its y_true row is non-zero, otherwise VOID (a class index >= 4 of a
+ * mask file, the fill_class = 255 padding of a crop or a mosaic: an all-zero one-hot row).  The cross-entropy entries above
+ * ignore a void pixel as they stand (zero term, zero gradient).  The _void entries below are their dice and bootstrapped twins,
+ * argument for argument, with void pixels left out; without a void pixel every output equals the twin's bit for bit.
+ *   dice / dice_square: T_c sums over the labelled pixels only (I_c has no void term anyway), loss and coef are formed from I, T
+ *   as before, and dL/dp of a void pixel is an exact zero row (its dz is +0).  An image without a labelled pixel has loss 0.
+ *   bootstrapped: keep [n] (int32, written) = min(L, max(1, ceil(keep_fraction L))) in double from L = the image's labelled
+ *   pixels, counted on the device (0 for L = 0; 0 < keep_fraction <= 1); thresh = the keep-th largest LABELLED l (+inf for
+ *   L = 0); a void pixel is never kept nor counted in kept and its gradient row is zero: its stored pixel_loss is -1, below
+ *   every thresh.  No host synchronisation.  prob, kept, loss may be NULL. */
+int ssdseg_mask_head_fwd_dice_void(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx,
+                                   const float* y_true, const float* class_weights_host, int squared, float* prob, float* loss,
+                                   float* coef);
+int ssdseg_mask_head_bwd_dice_void(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx,
+                                   const float* y_true, const float* coef, int squared, float loss_scale, float* dlogits);
+int ssdseg_mask_head_fwd_bootstrap_void(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx,
+                                        const float* y_true, const float* class_weights_host, double keep_fraction, float* prob,
+                                        float* pixel_loss, float* thresh, int* keep, int* kept, float* loss);
+int ssdseg_mask_head_bwd_bootstrap_void(ssdseg_ctx* ctx, const float* logits, int n, int h, int wdt, int c, int fy, int fx,
+                                        const float* y_true, const float* class_weights_host, const float* pixel_loss,
+                                        const float* thresh, float loss_scale, float* dlogits);
+int ssdseg_bootstrap_ce_loss_void(ssdseg_ctx* ctx, const float* y_true, const float* p, int n, int hw, int c,
+                                  const float* class_weights_host, double keep_fraction, float* loss);
 /* SSD head plumbing: Reshape(-1, 4) + Concatenate(axis=1) (blocks.py:155; models.py:256,271).  Forward: the activated
  * head tensor of one feature map, in[b][in_img_elems] (channel of element r = r % c), is written to
  * out[b][out_off_elems + r] of a buffer with out_img_elems floats per image.  reverse != 0 copies the other way
@@ -434,6 +457,9 @@ int ssdseg_topk_mask(ssdseg_ctx* ctx, const float* values, int n, int k, uint8_t
 /* dice / dice_square (losses.py:175-264), API surface only: loss[n] from y_true, p [n][hw][c]; n <= 65535 */
 int ssdseg_dice_loss(ssdseg_ctx* ctx, const float* y_true, const float* p, int n, int hw, int c,
                      const float* class_weights_host, int squared, float* loss);
+/* the same with void pixels (all-zero y_true rows) left out of T_c, as ssdseg_mask_head_fwd_dice_void; squared 0 or 1 */
+int ssdseg_dice_loss_void(ssdseg_ctx* ctx, const float* y_true, const float* p, int n, int hw, int c,
+                          const float* class_weights_host, int squared, float* loss);
 
 /* ---------------------------------------------------------------- K16: anchor matching + offset encoding
  * DataEncoderDecoder._encode_ground_truth_labels_boxes (datacoder.py:205-300).
@@ -549,6 +575,9 @@ int ssdseg_mosaic_gt(ssdseg_ctx* ctx, const float* src_gt, const int32_t* src_cn
  *   src = probabilities [n][h][w][4], fy = fx = 1.  y_true [n][h*fy][w*fx][4].  out [n].  n <= 65535. */
 int ssdseg_metric_mask_iou(ssdseg_ctx* ctx, const float* src, int n, int h, int wdt, int c, int fy, int fx, int from_logits,
                            const float* y_true, const float* class_weights_host, float* out);
+/* the same metric with total = sum (t + p) over the LABELLED pixels only (a pixel whose y_true row is all zero is void) */
+int ssdseg_metric_mask_iou_void(ssdseg_ctx* ctx, const float* src, int n, int h, int wdt, int c, int fy, int fx, int from_logits,
+                                const float* y_true, const float* class_weights_host, float* out);
 /* categorical_accuracy_metric (metrics.py:204-216): per class #anchors with one_hot(argmax p)[c] == y_true[c], / a,
  *   weighted sum over classes.  y_true, y_pred [b][a][4]; out [b]. */
 int ssdseg_metric_label_accuracy(ssdseg_ctx* ctx, const float* y_true, const float* y_pred, int b, int a, int c,
@@ -580,6 +609,15 @@ int ssdseg_seg_suppress(ssdseg_ctx* ctx, const float* mask_prob, int n_pixels_to
  *   T = sum (y + p), iou_out [n][c] = I / (T - I + 1e-7) (evaluators.py:236-241; the mean over the samples is the caller's).
  *   1 <= c <= 8.  Block partials in the ctx workspace, added in index order in double: the same bits on every run. */
 int ssdseg_eval_mask_jaccard(ssdseg_ctx* ctx, const float* prob, const uint8_t* mask_index_u8, int n, int hw, int c, float* iou_out);
+/* The same pass with the segmentation protocol's two options; the probabilities are read once for all three outputs.
+ *   ignore_void != 0: T sums over the labelled pixels only (index < c); a void pixel (index >= c) then enters neither I nor T.
+ *   confusion_out [n][c][c] (int32, rows true, columns predicted): for every labelled pixel of true class k,
+ *   confusion[k][argmax_j p_j] += 1, the lowest index among equal probabilities (np.argmax); void pixels enter no row, whatever
+ *   ignore_void says.  void_out [n]: the image's pixels with an index >= c.  Integer counts, folded in a fixed order.
+ *   iou_out, confusion_out and void_out may each be NULL (not all three).  With ignore_void == 0 iou_out holds the bits of
+ *   ssdseg_eval_mask_jaccard.  n <= 65535, hw < 2^28, 1 <= c <= 8. */
+int ssdseg_eval_mask_scores(ssdseg_ctx* ctx, const float* prob, const uint8_t* mask_index_u8, int n, int hw, int c, int ignore_void,
+                            float* iou_out, int32_t* confusion_out, int32_t* void_out);
 /* The IoU step of average_precision_object_detection (evaluators.py:6-62 inside :65-186): det [n][r][6] = (label, confidence,
  *   xmin, ymin, xmax, ymax) as ssdseg_combined_nms writes it, gt [n][gmax][5] = (label, xmin, ymin, xmax, ymax) and gt_count [n]
  *   as ssdseg_gather_gt / the compact loader hold them; best_out [n][r] = the largest IoU of the prediction with a ground-truth

@@ -345,7 +345,9 @@ __global__ void __launch_bounds__(256) focal_grad_kernel(const float* __restrict
     }
 }
 
-// ---- dice / dice_square: per image (intersection_c, total_c) over the pixels
+// ---- dice / dice_square: per image (intersection_c, total_c) over the pixels.  VOID: a void pixel (all-zero y row) adds nothing to
+// total_c: its terms are formed from zero probabilities
+template <bool VOID>
 __global__ void __launch_bounds__(256) dice_partial_kernel(const float* __restrict__ y, const float* __restrict__ p, int hw, int squared,
                                                            float* __restrict__ partial) {
     __shared__ float red[256];
@@ -353,7 +355,9 @@ __global__ void __launch_bounds__(256) dice_partial_kernel(const float* __restri
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
         const long long o = ((long long)img * hw + i) * 4;
-        const float4 a = ld4(y + o), b = ld4(p + o);
+        const float4 a = ld4(y + o);
+        const bool lab = !VOID || a.x != 0.f || a.y != 0.f || a.z != 0.f || a.w != 0.f;
+        const float4 b = lab ? ld4(p + o) : make_float4(0.f, 0.f, 0.f, 0.f);
         if (squared == 2) {   // weighted cross-entropy on probabilities (losses.py:294-299): acc[c] = -sum y*log(clip p)
             acc[0] -= a.x * logf(clipf(b.x)); acc[1] -= a.y * logf(clipf(b.y)); acc[2] -= a.z * logf(clipf(b.z)); acc[3] -= a.w * logf(clipf(b.w));
             continue;
@@ -423,6 +427,25 @@ int det_loss_launch(ssdseg_ctx* ctx, const float* y_labels, const float* p_label
 
 }  // namespace
 
+// dice / dice_square from given probabilities: both public entries launch through here
+namespace {
+template <bool VOID>
+int dice_loss_launch(ssdseg_ctx* ctx, const float* y_true, const float* p, int n, int hw, const float* class_weights_host, int squared, float* loss) {
+    int nblk = (hw + 2047) / 2048;
+    if (nblk > 64) nblk = 64;
+    void* ws;
+    int rc = ssdseg_workspace(ctx, (size_t)n * nblk * 8 * sizeof(float), &ws);
+    if (rc) return rc;
+    SSDSEG_LAUNCH_NAMED(ctx, VOID ? "dice_partial_kernel<VOID>" : "dice_partial_kernel", 32.0 * n * hw, 0.0, dice_partial_kernel<VOID>, dim3(nblk, n),
+                        dim3(256), 0, y_true, p, hw, squared, (float*)ws);
+    SSDSEG_LAUNCH_CHECK();
+    SSDSEG_LAUNCH(ctx, 0.0, 0.0, dice_finish_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (const float*)ws, nblk, n,
+                  make_float4(class_weights_host[0], class_weights_host[1], class_weights_host[2], class_weights_host[3]), squared, loss);
+    SSDSEG_LAUNCH_CHECK();
+    return 0;
+}
+}  // namespace
+
 extern "C" {
 
 int ssdseg_topk_mask(ssdseg_ctx* ctx, const float* values, int n, int k, uint8_t* mask) {
@@ -489,26 +512,26 @@ int ssdseg_det_loss_focal(ssdseg_ctx* ctx, const float* y_labels, const float* p
     return 0;
 }
 
+#define DICE_LOSS_ARGS()                                                                                     \
+    SSDSEG_ARG(ctx != nullptr, 1);                                                                           \
+    SSDSEG_ARG(y_true != nullptr, 2);                                                                        \
+    SSDSEG_ARG(p != nullptr, 3);                                                                             \
+    SSDSEG_ARG(n > 0 && n <= 65535 && hw > 0, 4);   /* the image is gridDim.y of dice_partial_kernel */      \
+    SSDSEG_ARG(c == 4, 6);                                                                                   \
+    SSDSEG_ARG(class_weights_host != nullptr, 7);                                                            \
+    SSDSEG_ARG(loss != nullptr, 9)
+
 int ssdseg_dice_loss(ssdseg_ctx* ctx, const float* y_true, const float* p, int n, int hw, int c, const float* class_weights_host,
                      int squared, float* loss) {
-    SSDSEG_ARG(ctx != nullptr, 1);
-    SSDSEG_ARG(y_true != nullptr, 2);
-    SSDSEG_ARG(p != nullptr, 3);
-    SSDSEG_ARG(n > 0 && n <= 65535 && hw > 0, 4);   // the image is gridDim.y of dice_partial_kernel
-    SSDSEG_ARG(c == 4, 6);
-    SSDSEG_ARG(class_weights_host != nullptr, 7);
-    SSDSEG_ARG(loss != nullptr, 9);
-    int nblk = (hw + 2047) / 2048;
-    if (nblk > 64) nblk = 64;
-    void* ws;
-    int rc = ssdseg_workspace(ctx, (size_t)n * nblk * 8 * sizeof(float), &ws);
-    if (rc) return rc;
-    SSDSEG_LAUNCH(ctx, 32.0 * n * hw, 0.0, dice_partial_kernel, dim3(nblk, n), dim3(256), 0, y_true, p, hw, squared, (float*)ws);
-    SSDSEG_LAUNCH_CHECK();
-    SSDSEG_LAUNCH(ctx, 0.0, 0.0, dice_finish_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (const float*)ws, nblk, n,
-                  make_float4(class_weights_host[0], class_weights_host[1], class_weights_host[2], class_weights_host[3]), squared, loss);
-    SSDSEG_LAUNCH_CHECK();
-    return 0;
+    DICE_LOSS_ARGS();
+    return dice_loss_launch<false>(ctx, y_true, p, n, hw, class_weights_host, squared, loss);
+}
+
+int ssdseg_dice_loss_void(ssdseg_ctx* ctx, const float* y_true, const float* p, int n, int hw, int c, const float* class_weights_host,
+                          int squared, float* loss) {
+    DICE_LOSS_ARGS();
+    SSDSEG_ARG(squared == 0 || squared == 1, 8);    // (the cross-entropy of mode 2 ignores void as it stands)
+    return dice_loss_launch<true>(ctx, y_true, p, n, hw, class_weights_host, squared, loss);
 }
 
 }  // extern "C"

@@ -55,7 +55,9 @@ class _EvalStager:
     """A test batch (`datacoder.CompactBatch` or `ResidentBatch`, un-augmented) into an inference engine, and the engine's outputs
     into the numbers of NB03#cell21-29 without leaving the device: the batch's loader (no encoder, no targets) fills the engine's
     input and its own gt / cnt; the uint8 class indices go to ssdseg_eval_mask_jaccard as they are, the ground-truth rows to
-    ssdseg_eval_det_best_iou.  Per batch: iou (n, c), and per NMS threshold pair the detection rows (n, r, 6) and their best IoU (n, r)."""
+    ssdseg_eval_det_best_iou.  Per batch: iou (n, c), and per NMS threshold pair the detection rows (n, r, 6) and their best IoU (n, r).
+    With `ignore_void` or `confusion` the mask step is ssdseg_eval_mask_scores instead: the same single pass over the probabilities,
+    which also leaves the per-image confusion counts (n, c, c) and void pixels (n,)."""
 
     def __init__(self, eng: E.Engine):
         self.eng, self.ctx = eng, eng.ctx
@@ -72,6 +74,7 @@ class _EvalStager:
         self.det = ctx.empty((b, self.r, 6))
         self.best = ctx.empty((b, self.r))
         self.iou = ctx.empty((b, self.prob.c))
+        self.confusion = self.void = None                       # allocated by the first call that asks for the confusion counts
 
     def load(self, batch):
         """the batch through its loader (pixels -> the engine's input, ground truth -> ld.gt / ld.cnt) -> (ld, its class indices [b][hw])"""
@@ -90,9 +93,10 @@ class _EvalStager:
             self.midx.view(i * hw, (hw,)).copy_from(ds.masks.view(int(s) * hw, (hw,)))
         return ld, self.midx
 
-    def run(self, batch, pairs):
-        """-> iou (n, c) float32, {pair: (detections (n, r, 6), best IoU (n, r))}: one network forward, one decode (+ segmentation
-        suppression), then per threshold pair the NMS and the best-IoU kernel"""
+    def run(self, batch, pairs, ignore_void=False, confusion=False):
+        """-> iou (n, c) float32, {pair: (detections (n, r, 6), best IoU (n, r))}, counts: one network forward, one decode (+
+        segmentation suppression), then per threshold pair the NMS and the best-IoU kernel.  counts: None, or with `confusion`
+        (confusion (n, c, c), void pixels (n,)) as int32"""
         eng, ctx, op, b = self.eng, self.ctx, self.nms_op, self.eng.batch
         ld, midx = self.load(batch)
         op.defer_nms = True
@@ -100,23 +104,41 @@ class _EvalStager:
             eng.forward()
         finally:
             op.defer_nms = False
-        ctx.call("ssdseg_eval_mask_jaccard", self.prob.buf, midx, b, self.prob.h * self.prob.w, self.prob.c, self.iou)
+        counts = None
+        if not (ignore_void or confusion):
+            ctx.call("ssdseg_eval_mask_jaccard", self.prob.buf, midx, b, self.prob.h * self.prob.w, self.prob.c, self.iou)
+        else:
+            if confusion and self.confusion is None:
+                self.confusion, self.void = ctx.empty((b, self.prob.c, self.prob.c), np.int32), ctx.empty(b, np.int32)
+            ctx.call("ssdseg_eval_mask_scores", self.prob.buf, midx, b, self.prob.h * self.prob.w, self.prob.c, int(ignore_void), self.iou,
+                     self.confusion if confusion else None, self.void if confusion else None)
+            if confusion:
+                counts = (self.confusion.download(), self.void.download())
         iou = self.iou.download()
         out = {}
         for pair in pairs:
             op.run_nms(pair[0], pair[1], out=self.det)
             ctx.call("ssdseg_eval_det_best_iou", self.det, ld.gt, ld.cnt, b, self.r, ld.GMAX, self.best)
             out[pair] = (self.det.download(), self.best.download())
-        return iou, out
+        return iou, out, counts
+
+
+def _eval_stager(model: K.Model, batch) -> _EvalStager:
+    eng = E.engine_for(model, len(batch), False)
+    if eng.eval_stager is None:
+        eng.eval_stager = _EvalStager(eng)
+    return eng.eval_stager
 
 
 def run_evaluate(model: K.Model, batch, pairs):
     """evaluators.evaluate_on_device's device side for one batch: (iou, {pair: (detections, best IoU)}), see _EvalStager.run.  A
     batch of another size gets an engine of its own, as in predict."""
-    eng = E.engine_for(model, len(batch), False)
-    if eng.eval_stager is None:
-        eng.eval_stager = _EvalStager(eng)
-    return eng.eval_stager.run(batch, pairs)
+    return _eval_stager(model, batch).run(batch, pairs)[:2]
+
+
+def run_evaluate_scores(model: K.Model, batch, pairs, ignore_void: bool, confusion: bool):
+    """run_evaluate with evaluate_on_device's mask options: (iou, {pair: ...}, None | (confusion (n, c, c), void pixels (n,)))"""
+    return _eval_stager(model, batch).run(batch, pairs, ignore_void, confusion)
 
 
 def run_train_on_batch(model: K.Model, x, y=None) -> Dict[str, float]:

@@ -124,6 +124,11 @@ _SIGNATURES = {
     "ssdseg_mask_head_fwd_bootstrap": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_f), _i, _vp, _vp, _vp, _vp, _vp],
     "ssdseg_mask_head_bwd_bootstrap": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_f), _vp, _vp, _f, _vp],
     "ssdseg_bootstrap_ce_loss": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), _i, _vp],
+    "ssdseg_mask_head_fwd_dice_void": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_f), _i, _vp, _vp, _vp],
+    "ssdseg_mask_head_bwd_dice_void": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _f, _vp],
+    "ssdseg_mask_head_fwd_bootstrap_void": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_f), _d, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ssdseg_mask_head_bwd_bootstrap_void": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_f), _vp, _vp, _f, _vp],
+    "ssdseg_bootstrap_ce_loss_void": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), _d, _vp],
     "ssdseg_head_gather": [_vp, _VP, _vp, _i, _i, _i, _i, _i, _i],
     "ssdseg_softmax_rows": [_vp, _VP, _vp, _i, _i],
     "ssdseg_det_loss": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
@@ -132,11 +137,13 @@ _SIGNATURES = {
     "ssdseg_loc_loss_iou": [_vp, _vp, _vp, _vp, C.POINTER(_f), _i, _i, _i, _f, _f, _vp, _vp],
     "ssdseg_topk_mask": [_vp, _vp, _i, _i, _vp],
     "ssdseg_dice_loss": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), _i, _vp],
+    "ssdseg_dice_loss_void": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), _i, _vp],
     "ssdseg_act_bwd": [_vp, _vp, _i, _vp, _i, _i, _i, _i],
     "ssdseg_channel_gather": [_vp, _VP, _i, _vp, _i, C.c_longlong, _i, _vp, _i],
     "ssdseg_copy2d": [_vp, _vp, _i, _vp, _i, _i, _i],
     "ssdseg_copy2d_batch": [_vp, _vp, _i, _i, C.c_longlong],
     "ssdseg_metric_mask_iou": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_f), _vp],
+    "ssdseg_metric_mask_iou_void": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_f), _vp],
     "ssdseg_metric_label_accuracy": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), _vp],
     "ssdseg_metric_box_iou": [_vp, _vp, _vp, _vp, C.POINTER(_f), _i, _i, _vp],
     "ssdseg_expand_inputs": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i],
@@ -153,6 +160,7 @@ _SIGNATURES = {
     "ssdseg_combined_nms": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp],
     "ssdseg_seg_suppress": [_vp, _vp, _i, _i, _vp, _i, _vp],
     "ssdseg_eval_mask_jaccard": [_vp, _vp, _vp, _i, _i, _i, _vp],
+    "ssdseg_eval_mask_scores": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "ssdseg_eval_det_best_iou": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "ssdseg_adam_step": [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _f],
     "ssdseg_sgd_step": [_vp, _vp, _vp, _vp, _sz, _f, _f, _i, _f, _vp, _vp, _i],

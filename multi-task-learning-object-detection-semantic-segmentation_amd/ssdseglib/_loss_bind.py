@@ -38,6 +38,11 @@ def _head(op: MaskHeadOp):
     return s.buf, s.n, s.h, s.w, s.c, op.fy, op.fx, op.y_true
 
 
+def _void_suffix(fn) -> str:
+    """what `ignore_void` on a loss or metric callable adds to its entries' names"""
+    return "_void" if getattr(fn, "ignore_void", False) else ""
+
+
 class CrossEntropy:
     """losses.cross_entropy (reference losses.py:294-305)"""
 
@@ -52,17 +57,18 @@ class CrossEntropy:
 
 
 class Dice:
-    """losses.dice / dice_square (reference losses.py:175-262)"""
+    """losses.dice / dice_square (reference losses.py:175-262); `ignore_void` on the callable selects the _void pair"""
 
     def __init__(self, fn, ctx, batch, pixels, squared=0):
         self.kind, self.squared = fn.loss_kind, squared
+        self.void = _void_suffix(fn)
         self.coef = ctx.empty((batch, 8))           # per-image backward coefficients left by the forward
 
     def fwd(self, op, prob):
-        op.e.ctx.call("ssdseg_mask_head_fwd_dice", *_head(op), op.class_weights, self.squared, prob, op.loss, self.coef)
+        op.e.ctx.call("ssdseg_mask_head_fwd_dice" + self.void, *_head(op), op.class_weights, self.squared, prob, op.loss, self.coef)
 
     def bwd(self, op, g):
-        op.e.ctx.call("ssdseg_mask_head_bwd_dice", *_head(op), self.coef, self.squared, op.loss_scale, g)
+        op.e.ctx.call("ssdseg_mask_head_bwd_dice" + self.void, *_head(op), self.coef, self.squared, op.loss_scale, g)
 
 
 class Bootstrapped:
@@ -79,6 +85,22 @@ class Bootstrapped:
 
     def bwd(self, op, g):
         op.e.ctx.call("ssdseg_mask_head_bwd_bootstrap", *_head(op), op.class_weights, self.pixel_loss, self.thresh, op.loss_scale, g)
+
+
+class BootstrappedVoid(Bootstrapped):
+    """bootstrapped_cross_entropy(..., ignore_void=True): `keep` is a device buffer [n], written by the forward from the labelled
+    pixels of the batch the device sees (crop and mosaic happen there); no host synchronisation"""
+
+    def __init__(self, fn, ctx, batch, pixels):
+        self.kind, self.keep_fraction, self.keep = fn.loss_kind, float(fn.keep_fraction), ctx.empty(batch, np.int32)
+        self.pixel_loss, self.thresh, self.kept = ctx.empty((batch, pixels)), ctx.empty(batch), ctx.empty(batch, np.int32)
+
+    def fwd(self, op, prob):
+        op.e.ctx.call("ssdseg_mask_head_fwd_bootstrap_void", *_head(op), op.class_weights, self.keep_fraction, prob, self.pixel_loss,
+                      self.thresh, self.keep, self.kept, op.loss)
+
+    def bwd(self, op, g):
+        op.e.ctx.call("ssdseg_mask_head_bwd_bootstrap_void", *_head(op), op.class_weights, self.pixel_loss, self.thresh, op.loss_scale, g)
 
 
 # ====================================================================================================== detection-loss variants
@@ -145,7 +167,7 @@ LOSSES = {
     "cross_entropy": ("mask", CrossEntropy),
     "dice": ("mask", Dice),
     "dice_square": ("mask", partial(Dice, squared=1)),
-    "bootstrapped_cross_entropy": ("mask", Bootstrapped),
+    "bootstrapped_cross_entropy": ("mask", lambda fn, *args: (BootstrappedVoid if _void_suffix(fn) else Bootstrapped)(fn, *args)),
 }
 
 
@@ -220,7 +242,7 @@ def bind_losses(eng, loss: dict, loss_weights: dict):
 # ====================================================================================================== metrics
 def _mask_iou(ctx, fn, op, out):
     s = op.logits.store
-    ctx.call("ssdseg_metric_mask_iou", s.buf, s.n, s.h, s.w, s.c, op.fy, op.fx, 1, op.y_true, fn._cw, out)
+    ctx.call("ssdseg_metric_mask_iou" + _void_suffix(fn), s.buf, s.n, s.h, s.w, s.c, op.fy, op.fx, 1, op.y_true, fn._cw, out)
 
 
 def _label_accuracy(ctx, fn, op, out):

@@ -25,7 +25,9 @@ class ResidentDataset:
     permutation, flips and colour draws, and the device crops before it flips and colours (ssdseg_crop_inputs, ssdseg_crop_gt).
     `mosaic`: None, or a dict of random_mosaic's keywords plus optional `fill` / `fill_class`: every batch then carries a Mosaic over
     its own samples, drawn from the same Generator AFTER the epoch's plan likewise, and the device assembles each image from four
-    samples of the batch in the crop's place (ssdseg_mosaic_inputs, ssdseg_mosaic_gt).  Not together with `random_crop`."""
+    samples of the batch in the crop's place (ssdseg_mosaic_inputs, ssdseg_mosaic_gt).  Not together with `random_crop`.
+    In both, fill_class=255 (any index >= 4) is the void fill: what lies outside the samples gets all-zero one-hot rows, which
+    `cross_entropy` ignores as it stands and the other mask losses and the mask metric ignore with `ignore_void=True`."""
 
     GMAX = GMAX     # ground-truth rows per sample, the loaders' own
 

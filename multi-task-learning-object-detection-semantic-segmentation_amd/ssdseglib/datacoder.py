@@ -181,7 +181,9 @@ def augmentation_random_crop(image_batch, targets_batch=None, **options):
     drawn window per sample attached, targets_batch), the analogue of augmentation_rgb_channels on a compact batch.  options: the
     keywords of random_crop_windows plus `fill` (r, g, b) and `fill_class`.  The loader applies the windows on the GPU
     (ssdseg_crop_inputs, ssdseg_crop_gt) before the flip and the colour step.  Float (images, targets) batches are refused: their
-    anchors are already encoded and cannot be re-cropped."""
+    anchors are already encoded and cannot be re-cropped.  fill_class=255 (any index >= 4) is the void fill: the padding of a
+    zoom-out becomes all-zero one-hot rows, which `cross_entropy` ignores as it stands and the other mask losses and the mask metric
+    ignore with `ignore_void=True`; the default 0 labels the padding as background."""
     if not isinstance(image_batch, CompactBatch):
         raise ValueError("augmentation_random_crop takes a CompactBatch: a float (images, targets) batch holds encoded anchors that "
                          "cannot be re-cropped")
@@ -195,7 +197,8 @@ def augmentation_mosaic(image_batch, targets_batch=None, **options):
     """a random mosaic for a CompactBatch: returns (a new CompactBatch sharing its arrays, with a freshly drawn Mosaic over its own
     samples attached, targets_batch), the analogue of augmentation_random_crop.  options: the keywords of random_mosaic plus `fill`
     (r, g, b) and `fill_class`.  The loader assembles the images on the GPU (ssdseg_mosaic_inputs, ssdseg_mosaic_gt) before the flip
-    and the colour step.  Float (images, targets) batches are refused: their anchors are already encoded."""
+    and the colour step.  Float (images, targets) batches are refused: their anchors are already encoded.  fill_class=255 is the void
+    fill, as in augmentation_random_crop."""
     if not isinstance(image_batch, CompactBatch):
         raise ValueError("augmentation_mosaic takes a CompactBatch: a float (images, targets) batch holds encoded anchors that cannot "
                          "be reassembled")

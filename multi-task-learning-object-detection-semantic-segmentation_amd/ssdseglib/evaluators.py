@@ -106,6 +106,39 @@ def jaccard_iou_semantic_segmentation(masks_pred_batch, path_files_masks: List[s
     return {l: float(v) for l, v in zip(labels_codes, iou) if l != label_code_background}
 
 
+def confusion_matrix_semantic_segmentation(masks_pred_batch, masks_true_index, n_classes: int) -> Tuple[np.ndarray, int]:
+    """The hard confusion matrix of saved predictions (not in the reference), and the spec of the device path
+    (ssdseg_eval_mask_scores).  masks_pred_batch: (N, H, W, C) probabilities; masks_true_index: (N, H, W) class indices (an
+    index >= n_classes is void).  For every labelled pixel of class k: M[k][argmax_c p_c] += 1, the lowest index among equal
+    probabilities (np.argmax); void pixels enter no row.  -> (M (C, C) int64, rows true and columns predicted; void pixels)"""
+    n_classes = int(n_classes)
+    pred = np.asarray(masks_pred_batch)
+    true = np.asarray(masks_true_index).astype(np.int64)
+    if pred.shape[-1] != n_classes or pred.shape[:-1] != true.shape:
+        raise ValueError(f"predictions {pred.shape} do not fit class indices {true.shape} with {n_classes} classes")
+    labelled = (true >= 0) & (true < n_classes)
+    cells = true[labelled] * n_classes + pred.argmax(axis=-1)[labelled]
+    m = np.bincount(cells, minlength=n_classes * n_classes).reshape(n_classes, n_classes).astype(np.int64)
+    return m, int(true.size - labelled.sum())
+
+
+def scores_from_confusion(confusion, labels_codes: List[int]) -> Tuple[Dict[int, float], float, float]:
+    """-> (iou_hard {label: M_cc / (row_c + col_c - M_cc), NaN for a class neither labelled nor predicted}, miou: its mean over
+    the classes that are not NaN, background included (the VOC / Cityscapes convention; NaN when every class is),
+    pixel_accuracy: trace / sum (NaN for an empty matrix))"""
+    m = np.asarray(confusion, np.int64)
+    if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] != len(labels_codes):
+        raise ValueError(f"confusion matrix {m.shape} for {len(labels_codes)} label codes")
+    diag = np.diag(m).astype(np.float64)
+    den = (m.sum(axis=1) + m.sum(axis=0)).astype(np.float64) - diag
+    iou = np.full(m.shape[0], np.nan)
+    np.divide(diag, den, out=iou, where=den > 0)
+    seen = ~np.isnan(iou)
+    miou = float(iou[seen].mean()) if seen.any() else float("nan")
+    total = int(m.sum())
+    return {l: float(v) for l, v in zip(labels_codes, iou)}, miou, (float(np.trace(m)) / total if total else float("nan"))
+
+
 def _nms_layer(model_inference):
     for t in model_inference.outputs:
         if type(t.layer).__name__ == "NonMaximumSuppression":
@@ -150,7 +183,7 @@ def _labels_true(batch) -> List[np.ndarray]:
 
 
 def evaluate_on_device(model_inference, data, labels_codes: List[int], label_code_background: int, iou_thresholds: Sequence[float],
-                       nms_grid: Optional[Iterable[Tuple[float, float]]] = None) -> dict:
+                       nms_grid: Optional[Iterable[Tuple[float, float]]] = None, ignore_void: bool = False, confusion: bool = False) -> dict:
     """The test-set evaluation of NB03#cell21-29 on a set the device holds.
 
     model_inference: from `get_model_for_inference` (suppress_background_boxes=False: with True the detections lose their batch
@@ -164,7 +197,20 @@ def evaluate_on_device(model_inference, data, labels_codes: List[int], label_cod
         'ap': {(b_thr, p_thr): {iou_threshold: {label: average precision}}},
         'detections': {(b_thr, p_thr): (N, r, 6) rows (label, confidence, xmin, ymin, xmax, ymax)}}
     without the background in 'iou' and 'ap', as jaccard_iou_semantic_segmentation / average_precision_object_detection, whose
-    values these are (rows of label 0 are empty NMS rows and never count as predictions)."""
+    values these are (rows of label 0 are empty NMS rows and never count as predictions).
+
+    ignore_void=True: 'iou' sums total = sum (y + p) over the labelled pixels only; a void pixel (class index >= the number of
+    classes) then enters neither sum.  confusion=True adds the hard scores every segmentation paper reports, from arg-max
+    predictions accumulated over the whole set with void excluded (whatever ignore_void says):
+        'confusion': (C, C) int64, rows true, columns predicted;  'void_pixels': int;
+        'iou_hard': {label: IoU} for EVERY label code, background included (NaN for an absent class);
+        'miou': their mean without the NaNs;  'pixel_accuracy': trace / sum
+    (confusion_matrix_semantic_segmentation / scores_from_confusion on `predict`'s masks).  Either option sends the batch through
+    ssdseg_eval_mask_scores: the probabilities are still read once."""
+    from .losses import void_flag
+    ignore_void = void_flag(ignore_void)
+    if not isinstance(confusion, (bool, np.bool_)):
+        raise ValueError(f"confusion must be a bool, got {confusion!r}")
     nms = _nms_layer(model_inference)
     if nms.suppress_background_boxes:
         raise ValueError("evaluate_on_device: suppress_background_boxes=True drops the batch axis of the detections (quirk Q7)")
@@ -182,10 +228,17 @@ def evaluate_on_device(model_inference, data, labels_codes: List[int], label_cod
     n_true = {l: 0 for l in classes}
     detections = {pair: [] for pair in pairs}
     iou_sum, seen = np.zeros(n_cls, np.float64), 0
+    matrix, void_pixels = np.zeros((n_cls, n_cls), np.int64), 0
 
     from . import _fit
     for batch in _plain_batches(data):
-        iou, per_pair = _fit.run_evaluate(model_inference, batch, pairs)
+        if ignore_void or confusion:
+            iou, per_pair, counts = _fit.run_evaluate_scores(model_inference, batch, pairs, ignore_void, bool(confusion))
+            if counts is not None:
+                matrix += counts[0].astype(np.int64).sum(axis=0)
+                void_pixels += int(counts[1].astype(np.int64).sum())
+        else:
+            iou, per_pair = _fit.run_evaluate(model_inference, batch, pairs)
         for row in iou:
             iou_sum += row.astype(np.float64)
             seen += 1
@@ -203,6 +256,10 @@ def evaluate_on_device(model_inference, data, labels_codes: List[int], label_cod
     if seen == 0:
         raise ValueError("evaluate_on_device: no samples")
     mean = iou_sum / seen
-    return {"iou": {l: float(v) for l, v in zip(labels_codes, mean) if l != label_code_background},
-            "ap": {pair: {t: _average_precision_from_hits(hits[pair][t], n_true, classes) for t in thresholds} for pair in pairs},
-            "detections": {pair: np.concatenate(detections[pair], axis=0) for pair in pairs}}
+    result = {"iou": {l: float(v) for l, v in zip(labels_codes, mean) if l != label_code_background},
+              "ap": {pair: {t: _average_precision_from_hits(hits[pair][t], n_true, classes) for t in thresholds} for pair in pairs},
+              "detections": {pair: np.concatenate(detections[pair], axis=0) for pair in pairs}}
+    if confusion:
+        iou_hard, miou, accuracy = scores_from_confusion(matrix, labels_codes)
+        result.update(confusion=matrix, void_pixels=void_pixels, iou_hard=iou_hard, miou=miou, pixel_accuracy=accuracy)
+    return result

@@ -152,16 +152,25 @@ def iou_localization_loss(center_x_boxes_default, center_y_boxes_default, width_
     return loss_fn
 
 
-def _mask_loss(mode: int, name: str, kind: str, classes_weights: List[float]) -> Callable:
+def void_flag(ignore_void) -> bool:
+    """the `ignore_void` option of the mask losses and of the mask metric: a bool, nothing that merely converts to one"""
+    if not isinstance(ignore_void, (bool, np.bool_)):
+        raise ValueError(f"ignore_void must be a bool, got {ignore_void!r}")
+    return bool(ignore_void)
+
+
+def _mask_loss(mode: int, name: str, kind: str, classes_weights: List[float], ignore_void: bool = False) -> Callable:
     weights = tuple(float(w) for w in classes_weights)
+    entry = "ssdseg_dice_loss_void" if void_flag(ignore_void) else "ssdseg_dice_loss"
 
     def loss_fn(y_true, y_pred):
         n, *hw, c = shape_of(y_true)
-        return per_sample("ssdseg_dice_loss", n, dev(y_true), dev(y_pred), n, int(np.prod(hw)), c, c4(weights), mode, OUT)
+        return per_sample(entry, n, dev(y_true), dev(y_pred), n, int(np.prod(hw)), c, c4(weights), mode, OUT)
 
     loss_fn.__name__ = name
     loss_fn.classes_weights = weights
     loss_fn.loss_kind = kind
+    loss_fn.ignore_void = bool(ignore_void)
     return loss_fn
 
 
@@ -170,12 +179,18 @@ def bootstrap_keep(keep_fraction: float, pixels: int) -> int:
     return min(int(pixels), max(1, math.ceil(float(keep_fraction) * int(pixels))))
 
 
-def bootstrapped_cross_entropy(classes_weights: List[float], keep_fraction: float = 0.25) -> Callable:
+def bootstrapped_cross_entropy(classes_weights: List[float], keep_fraction: float = 0.25, ignore_void: bool = False) -> Callable:
     """weighted pixel cross-entropy over the hardest pixels of each image only (hard-pixel mining, DeepLab's bootstrapped
     cross-entropy; not in the reference): with l_i = -sum_c w_c y_ic log(clip p_ic) the `cross_entropy` term of pixel i and
     keep = min(H W, max(1, ceil(keep_fraction H W))), an image's loss is the sum of the l_i >= its keep-th largest l.  Every pixel
     tied with the keep-th value is kept (no tie-break by index), so more than `keep` pixels may count.  The selection is per
-    image: no image depends on the rest of its batch.  keep_fraction = 1 is `cross_entropy`."""
+    image: no image depends on the rest of its batch.  keep_fraction = 1 is `cross_entropy`.
+
+    ignore_void=True: void pixels (all-zero y_true rows: a class index >= 4, the fill_class=255 padding of a crop or a mosaic) are
+    never kept, and keep is formed per image ON THE DEVICE from L, the image's labelled pixels, in place of H W -- after a
+    zoom-out that leaves 1/16 of the image labelled, keep_fraction=0.25 still mines a quarter of what is labelled.  An image
+    without a labelled pixel has loss 0 and a zero gradient."""
+    ignore_void = void_flag(ignore_void)
     try:
         weights = tuple(float(w) for w in classes_weights)
     except TypeError:
@@ -194,26 +209,32 @@ def bootstrapped_cross_entropy(classes_weights: List[float], keep_fraction: floa
     def loss_fn(y_true, y_pred):
         n, *hw, c = shape_of(y_true)
         hw = int(np.prod(hw))
+        if ignore_void:
+            return per_sample("ssdseg_bootstrap_ce_loss_void", n, dev(y_true), dev(y_pred), n, hw, c, c4(weights), keep_fraction, OUT)
         return per_sample("ssdseg_bootstrap_ce_loss", n, dev(y_true), dev(y_pred), n, hw, c, c4(weights), bootstrap_keep(keep_fraction, hw), OUT)
 
     loss_fn.__name__ = "bootstrapped_cross_entropy_loss"
     loss_fn.classes_weights = weights
     loss_fn.keep_fraction = keep_fraction
+    loss_fn.ignore_void = ignore_void
     loss_fn.loss_kind = "bootstrapped_cross_entropy"
     return loss_fn
 
 
-def dice(classes_weights: List[float]) -> Callable:
-    """weighted dice loss on probabilities (reference losses.py:204-216)."""
-    return _mask_loss(0, "dice_loss", "dice", classes_weights)
+def dice(classes_weights: List[float], ignore_void: bool = False) -> Callable:
+    """weighted dice loss on probabilities (reference losses.py:204-216).  ignore_void=True: a void pixel (all-zero y_true row) is
+    left out of T_c = sum (y_c + p_c) and gets a zero gradient; as the reference has it, its probabilities count as false
+    positives of every class."""
+    return _mask_loss(0, "dice_loss", "dice", classes_weights, ignore_void)
 
 
-def dice_square(classes_weights: List[float]) -> Callable:
-    """weighted squared-denominator dice loss (reference losses.py:250-262)."""
-    return _mask_loss(1, "dice_square_loss", "dice_square", classes_weights)
+def dice_square(classes_weights: List[float], ignore_void: bool = False) -> Callable:
+    """weighted squared-denominator dice loss (reference losses.py:250-262).  ignore_void: as `dice`."""
+    return _mask_loss(1, "dice_square_loss", "dice_square", classes_weights, ignore_void)
 
 
 def cross_entropy(classes_weights: List[float]) -> Callable:
     """weighted pixel cross-entropy on probabilities, summed over pixels and classes (reference losses.py:294-305);
-    the loss NB03#cell10 trains the mask head with."""
+    the loss NB03#cell10 trains the mask head with.  It ignores void pixels as it stands: an all-zero y_true row has a zero term
+    and a zero gradient, so it takes no `ignore_void` option."""
     return _mask_loss(2, "cross_entropy_loss", "cross_entropy", classes_weights)

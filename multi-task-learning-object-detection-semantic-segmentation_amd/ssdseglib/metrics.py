@@ -13,21 +13,24 @@ from typing import Callable, List
 
 import numpy as np
 
-from .losses import OUT, _ctx, boxes_on_context, c4, dev, per_sample, shape_of
+from .losses import OUT, _ctx, boxes_on_context, c4, dev, per_sample, shape_of, void_flag
 
 
-def jaccard_iou_segmentation_masks(classes_weights: List[float]) -> Callable:
-    """reference metrics.py:5-50"""
+def jaccard_iou_segmentation_masks(classes_weights: List[float], ignore_void: bool = False) -> Callable:
+    """reference metrics.py:5-50.  ignore_void=True: total = sum (t + p) over the labelled pixels only (a pixel whose y_true row
+    is all zero is void), as the mask losses' option of the same name."""
     if len(classes_weights) != 4:
         raise ValueError("the segmentation metric kernel handles the reference's 4 classes (background + 3)")
     cw = c4(classes_weights)
+    entry = "ssdseg_metric_mask_iou_void" if void_flag(ignore_void) else "ssdseg_metric_mask_iou"
 
     def jaccard_iou_segmentation_masks_metric(y_true, y_pred):
         n, h, w, c = shape_of(y_pred)
-        return per_sample("ssdseg_metric_mask_iou", n, dev(y_pred), n, h, w, c, 1, 1, 0, dev(y_true), cw, OUT)
+        return per_sample(entry, n, dev(y_pred), n, h, w, c, 1, 1, 0, dev(y_true), cw, OUT)
 
     f = jaccard_iou_segmentation_masks_metric
     f.metric_kind, f.classes_weights, f._cw = "mask_iou", tuple(float(x) for x in classes_weights), cw
+    f.ignore_void = bool(ignore_void)
     return f
 
 
