@@ -598,6 +598,22 @@ int ssdseg_decode_boxes(ssdseg_ctx* ctx, const float* offsets, const float* anch
 int ssdseg_combined_nms(ssdseg_ctx* ctx, const float* corners, const float* probs, int b, int a, int c,
                         int max_per_class, int max_total, float iou_threshold, float score_threshold, float* out,
                         int32_t* valid);
+/* ssdseg_combined_nms with Gaussian Soft-NMS score decay (Bodla et al. 2017; the soft_nms_sigma of
+ * tf.image.non_max_suppression_with_scores, per class as above; TF's combined NMS has no soft form).  Same layouts and argument
+ * checks; soft_nms_sigma must be finite and > 0 (off is ssdseg_combined_nms itself).  Per image and class, every class competing:
+ *   1. s_i = probs[i][cls]; a candidate is alive iff s_i > score_threshold.
+ *   2. at most max_per_class times: pick the alive k with the largest CURRENT s (ties: lowest anchor), record (s_k, k, cls) with
+ *      the decayed score and kill k; for every alive i, iou = the hard kernel's IoU (raw corners, no +1, a degenerate box overlaps
+ *      nothing): iou > iou_threshold kills i, otherwise s_i = s_i * w and i dies if s_i <= score_threshold.
+ *   3. w = float32(exp(-0.5 * x * x / float64(soft_nms_sigma))), x = float64(iou), evaluated in double in that order: the
+ *      correctly rounded float32 weight on any host with an IEEE double exp, so a host restatement (layers.soft_nms_reference)
+ *      agrees bit for bit; iou == 0 gives w == 1 exactly.
+ *   4. merge as above: (decayed score desc, anchor asc, class asc), max_total rows (label, decayed score, xmin, ymin, xmax, ymax).
+ * iou_threshold = 1 is the pure Gaussian Soft-NMS (Bodla's sigma = 2 * soft_nms_sigma); a sigma so large that every w rounds to
+ * 1 (1e30) gives the bytes of ssdseg_combined_nms.  No atomics, no host synchronisation: the same bytes on every run. */
+int ssdseg_combined_nms_soft(ssdseg_ctx* ctx, const float* corners, const float* probs, int b, int a, int c,
+                             int max_per_class, int max_total, float iou_threshold, float score_threshold,
+                             float soft_nms_sigma, float* out, int32_t* valid);
 /* SegmentationSuppression.call (layers.py:203-210): class-present flags over the WHOLE batch (quirk Q6) */
 int ssdseg_seg_suppress(ssdseg_ctx* ctx, const float* mask_prob, int n_pixels_total, int c, const float* probs,
                         int rows, float* probs_out);

@@ -3,6 +3,7 @@
 //   ssdseg_encode_targets  DataEncoderDecoder._encode_ground_truth_labels_boxes   reference datacoder.py:205-300
 //   ssdseg_decode_boxes    DecodeBoxesCentroidsOffsets.call                        reference layers.py:58-79
 //   ssdseg_combined_nms    NonMaximumSuppression.call -> tf.image.combined_non_max_suppression + repack  layers.py:141-162
+//   ssdseg_combined_nms_soft  the same with Gaussian Soft-NMS score decay (no reference counterpart; definition at the kernel)
 //   ssdseg_seg_suppress    SegmentationSuppression.call                             reference layers.py:203-210
 // One workgroup per image (encode) or per (class, image) (NMS); arg-max reductions carry (value, lowest index).
 #include "common.h"
@@ -171,9 +172,76 @@ __global__ void __launch_bounds__(NMS_T) nms_class_kernel(const float* __restric
     }
 }
 
-// one thread per image: merge the per-class picks, order by (score desc, anchor asc, class asc), keep max_total
-__global__ void nms_merge_kernel(const float* __restrict__ corners, const float* __restrict__ probs, const int* __restrict__ sel, int b, int a,
-                                 int c, int max_per_class, int max_total, float* __restrict__ out, int* __restrict__ valid) {
+// Soft-NMS (Bodla et al. 2017, Gaussian form, next to the hard step as in tf.image.non_max_suppression_with_scores): per class of
+// one image every candidate carries a CURRENT score s_i, initially probs[i][cls]; it is alive iff s_i > score_thr.  At most
+// max_per_class times: pick the alive candidate k with the largest current score (ties: lowest anchor), record (s_k, k) with the
+// decayed score, kill k; then for every alive i with iou = iou_tf(box_i, box_k): iou > iou_thr kills i (the hard step), otherwise
+// s_i = s_i * w and i dies once s_i <= score_thr.  The weight is DEFINED as w = float(exp(-0.5 * x * x / double(sigma))) with
+// x = double(iou), evaluated in double in that order (x * x is exact, the division and the exp round): the correctly rounded
+// float32 weight on any host with an IEEE double exp, as logcr in losses.hip, so the picks are reproducible bit for bit on the
+// host.  iou == 0 gives w == 1 exactly and skips the exp; scores only shrink, so a class's picks come out in non-increasing order.
+// iou_thr = 1 leaves the pure Gaussian Soft-NMS (Bodla's sigma = 2 * sigma); a sigma so large that every w rounds to 1 is the hard NMS.
+//
+// grid (classes, images) as nms_class_kernel.  A thread owns the anchors i = t (mod NMS_T) in every pass, so the current scores
+// need no barrier of their own, and the decay pass of one round is also the arg-max scan of the next.  The scores live in LDS
+// while 4 * a bytes fit beside the 8 KB of reduction arrays under 64 KB (a <= NMS_SOFT_LDS_A = 14336, so the 9600 anchors of the
+// model: 38 KB, two workgroups per CU); beyond that in a [b][c][a] row of the workspace, which the owning thread re-reads from L2.
+// A killed candidate holds -inf.  No atomics, the fold order of block_argmax is fixed: the same bytes on every run.
+constexpr int NMS_SOFT_LDS_A = (64 * 1024 - NMS_T * 8) / 4;
+template <bool IN_LDS>
+__global__ void __launch_bounds__(NMS_T) nms_soft_class_kernel(const float* __restrict__ corners, const float* __restrict__ probs, int a, int c,
+                                                               int max_per_class, float iou_thr, float score_thr, float sigma,
+                                                               float* __restrict__ cur_ws, int* __restrict__ sel, float* __restrict__ rec) {
+    extern __shared__ float cur_lds[];
+    __shared__ float rv[NMS_T];
+    __shared__ int ri[NMS_T];
+    const int cls = blockIdx.x, img = blockIdx.y, t = threadIdx.x;
+    const float* sc = probs + (long long)img * a * c + cls;
+    const float* bx = corners + (long long)img * a * 4;
+    float* cur = IN_LDS ? cur_lds : cur_ws + ((long long)img * c + cls) * a;
+    const double sg = (double)sigma;
+    int* out = sel + ((long long)img * c + cls) * max_per_class;
+    float* out_s = rec + ((long long)img * c + cls) * max_per_class;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = t; i < a; i += NMS_T) {
+        const float v = sc[(long long)i * c];
+        cur[i] = v;
+        if (v > score_thr && better(v, i, bv, bi)) { bv = v; bi = i; }
+    }
+    for (int r = 0; r < max_per_class; ++r) {
+        const Best b = block_argmax<NMS_T>(bv, bi, rv, ri);
+        if (b.i == 0x7fffffff) {                       // nothing left
+            if (t == 0) for (int q = r; q < max_per_class; ++q) out[q] = -1;
+            return;
+        }
+        if (t == 0) { out[r] = b.i; out_s[r] = b.v; }
+        if (r + 1 == max_per_class) return;
+        const float4 kb = ld4(bx + (long long)b.i * 4);
+        bv = -INFINITY;
+        bi = 0x7fffffff;
+        for (int i = t; i < a; i += NMS_T) {
+            float v = cur[i];
+            if (!(v > score_thr)) continue;            // dead: below the threshold from the start, decayed under it, or killed
+            if (i == b.i) { cur[i] = -INFINITY; continue; }
+            const float iou = iou_tf(ld4(bx + (long long)i * 4), kb);
+            if (iou > iou_thr) { cur[i] = -INFINITY; continue; }
+            if (iou != 0.f) {                          // (iou == 0: w == 1, the score keeps its bits)
+                const double x = (double)iou;
+                v = v * (float)exp(-0.5 * x * x / sg);
+                cur[i] = v;
+            }
+            if (v > score_thr && better(v, i, bv, bi)) { bv = v; bi = i; }
+        }
+    }
+}
+
+// one thread per image: merge the per-class picks, order by (score desc, anchor asc, class asc), keep max_total.  The score of a
+// pick is its probability, or with RECORDED the (decayed) score the soft kernel wrote next to it: rec [b][c][max_per_class]
+template <bool RECORDED>
+__global__ void nms_merge_kernel(const float* __restrict__ corners, const float* __restrict__ probs, const int* __restrict__ sel,
+                                 const float* __restrict__ rec, int b, int a, int c, int max_per_class, int max_total,
+                                 float* __restrict__ out, int* __restrict__ valid) {
     const int img = blockIdx.x * blockDim.x + threadIdx.x;
     if (img >= b) return;
     float* o = out + (long long)img * max_total * 6;
@@ -189,7 +257,7 @@ __global__ void nms_merge_kernel(const float* __restrict__ corners, const float*
             const int idx = sel[(long long)img * ncand + q];
             if (idx < 0) continue;
             const int cls = q / max_per_class;
-            const float s = probs[((long long)img * a + idx) * c + cls];
+            const float s = RECORDED ? rec[(long long)img * ncand + q] : probs[((long long)img * a + idx) * c + cls];
             if (taken > 0) {
                 const bool after = s < last_s || (s == last_s && (idx > last_i || (idx == last_i && cls > last_c)));
                 if (!after) continue;
@@ -234,6 +302,22 @@ __global__ void seg_apply_kernel(const float* __restrict__ probs, const int* __r
 
 constexpr int BOX_EW_CAP = 4096;   // blocks of the element-wise kernels of this unit (ew_blocks)
 
+// the argument checks both NMS entries make, reported under the entry's name: the layer and the evaluator never meet a shape that
+// one of them accepts and the other refuses.  `out_arg`: the position of `out` in the entry
+int nms_check(const char* entry, ssdseg_ctx* ctx, const float* corners, const float* probs, int b, int a, int c, int max_per_class,
+              int max_total, const float* out, int out_arg) {
+    SSDSEG_ARG_AS(entry, ctx != nullptr, 1);
+    SSDSEG_ARG_AS(entry, corners != nullptr, 2);
+    SSDSEG_ARG_AS(entry, probs != nullptr, 3);
+    SSDSEG_ARG_AS(entry, b > 0, 4);
+    SSDSEG_ARG_AS(entry, a > 0 && a <= 150000, 5);      // one byte of LDS per anchor (hard)
+    SSDSEG_ARG_AS(entry, c > 0 && c <= 64, 6);
+    SSDSEG_ARG_AS(entry, max_per_class > 0, 7);
+    SSDSEG_ARG_AS(entry, max_total > 0, 8);
+    SSDSEG_ARG_AS(entry, out != nullptr, out_arg);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -275,24 +359,46 @@ int ssdseg_decode_boxes(ssdseg_ctx* ctx, const float* offsets, const float* anch
 
 int ssdseg_combined_nms(ssdseg_ctx* ctx, const float* corners, const float* probs, int b, int a, int c, int max_per_class, int max_total,
                         float iou_threshold, float score_threshold, float* out, int32_t* valid) {
-    SSDSEG_ARG(ctx != nullptr, 1);
-    SSDSEG_ARG(corners != nullptr, 2);
-    SSDSEG_ARG(probs != nullptr, 3);
-    SSDSEG_ARG(b > 0, 4);
-    SSDSEG_ARG(a > 0 && a <= 150000, 5);      // one byte of LDS per anchor
-    SSDSEG_ARG(c > 0 && c <= 64, 6);
-    SSDSEG_ARG(max_per_class > 0, 7);
-    SSDSEG_ARG(max_total > 0, 8);
-    SSDSEG_ARG(out != nullptr, 11);
+    int rc = nms_check(__func__, ctx, corners, probs, b, a, c, max_per_class, max_total, out, 11);
+    if (rc) return rc;
     void* ws;
-    int rc = ssdseg_workspace(ctx, (size_t)b * c * max_per_class * sizeof(int), &ws);
+    rc = ssdseg_workspace(ctx, (size_t)b * c * max_per_class * sizeof(int), &ws);
     if (rc) return rc;
     int* sel = (int*)ws;
     SSDSEG_LAUNCH(ctx, 4.0 * b * a * (4 + c), 0.0, nms_class_kernel, dim3(c, b), dim3(NMS_T), (size_t)((a + 15) / 16 * 16), corners, probs, a, c,
                   max_per_class, iou_threshold, score_threshold, sel);
     SSDSEG_LAUNCH_CHECK();
-    SSDSEG_LAUNCH(ctx, 0.0, 0.0, nms_merge_kernel, dim3(cdiv(b, 64)), dim3(64), 0, corners, probs, (const int*)sel, b, a, c, max_per_class,
-                  max_total, out, valid);
+    SSDSEG_LAUNCH_NAMED(ctx, "nms_merge_kernel", 0.0, 0.0, nms_merge_kernel<false>, dim3(cdiv(b, 64)), dim3(64), 0, corners, probs, (const int*)sel,
+                        (const float*)nullptr, b, a, c, max_per_class, max_total, out, valid);
+    SSDSEG_LAUNCH_CHECK();
+    return 0;
+}
+
+int ssdseg_combined_nms_soft(ssdseg_ctx* ctx, const float* corners, const float* probs, int b, int a, int c, int max_per_class, int max_total,
+                             float iou_threshold, float score_threshold, float soft_nms_sigma, float* out, int32_t* valid) {
+    int rc = nms_check(__func__, ctx, corners, probs, b, a, c, max_per_class, max_total, out, 12);
+    if (rc) return rc;
+    SSDSEG_ARG(std::isfinite(soft_nms_sigma) && soft_nms_sigma > 0.f, 11);
+    // workspace: sel and the recorded scores [b][c][max_per_class] each, then the current scores [b][c][a] when they do not fit LDS
+    const size_t npick = (size_t)b * c * max_per_class;
+    const bool in_lds = a <= NMS_SOFT_LDS_A;
+    void* ws;
+    rc = ssdseg_workspace(ctx, npick * 8 + (in_lds ? 0 : (size_t)b * c * a * sizeof(float)), &ws);
+    if (rc) return rc;
+    int* sel = (int*)ws;
+    float* rec = (float*)ws + npick;
+    float* cur = rec + npick;
+    if (in_lds) {
+        SSDSEG_LAUNCH_NAMED(ctx, "nms_soft_class_kernel_lds", 4.0 * b * a * (4 + c), 0.0, nms_soft_class_kernel<true>, dim3(c, b), dim3(NMS_T),
+                            (size_t)((a + 3) / 4 * 16), corners, probs, a, c, max_per_class, iou_threshold, score_threshold, soft_nms_sigma,
+                            (float*)nullptr, sel, rec);
+    } else {
+        SSDSEG_LAUNCH_NAMED(ctx, "nms_soft_class_kernel_ws", 4.0 * b * a * (4 + 3 * c), 0.0, nms_soft_class_kernel<false>, dim3(c, b), dim3(NMS_T),
+                            0, corners, probs, a, c, max_per_class, iou_threshold, score_threshold, soft_nms_sigma, cur, sel, rec);
+    }
+    SSDSEG_LAUNCH_CHECK();
+    SSDSEG_LAUNCH_NAMED(ctx, "nms_merge_kernel_recorded", 0.0, 0.0, nms_merge_kernel<true>, dim3(cdiv(b, 64)), dim3(64), 0, corners, probs,
+                        (const int*)sel, (const float*)rec, b, a, c, max_per_class, max_total, out, valid);
     SSDSEG_LAUNCH_CHECK();
     return 0;
 }

@@ -95,7 +95,8 @@ class _EvalStager:
 
     def run(self, batch, pairs, ignore_void=False, confusion=False):
         """-> iou (n, c) float32, {pair: (detections (n, r, 6), best IoU (n, r))}, counts: one network forward, one decode (+
-        segmentation suppression), then per threshold pair the NMS and the best-IoU kernel.  counts: None, or with `confusion`
+        segmentation suppression), then per threshold pair (or triple with a Soft-NMS sigma; a pair runs the layer's own) the NMS
+        and the best-IoU kernel.  counts: None, or with `confusion`
         (confusion (n, c, c), void pixels (n,)) as int32"""
         eng, ctx, op, b = self.eng, self.ctx, self.nms_op, self.eng.batch
         ld, midx = self.load(batch)
@@ -117,7 +118,7 @@ class _EvalStager:
         iou = self.iou.download()
         out = {}
         for pair in pairs:
-            op.run_nms(pair[0], pair[1], out=self.det)
+            op.run_nms(pair[0], pair[1], pair[2] if len(pair) > 2 else None, out=self.det)     # (b_thr, p_thr[, Soft-NMS sigma])
             ctx.call("ssdseg_eval_det_best_iou", self.det, ld.gt, ld.cnt, b, self.r, ld.GMAX, self.best)
             out[pair] = (self.det.download(), self.best.download())
         return iou, out, counts

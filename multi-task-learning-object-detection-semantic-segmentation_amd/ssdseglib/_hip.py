@@ -158,6 +158,7 @@ _SIGNATURES = {
     "ssdseg_encode_targets": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, C.POINTER(_f), _vp, _vp, _vp],
     "ssdseg_decode_boxes": [_vp, _vp, _vp, _i, _i, C.POINTER(_f), _vp],
     "ssdseg_combined_nms": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp],
+    "ssdseg_combined_nms_soft": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp],
     "ssdseg_seg_suppress": [_vp, _vp, _i, _i, _vp, _i, _vp],
     "ssdseg_eval_mask_jaccard": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "ssdseg_eval_mask_scores": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],

@@ -705,16 +705,22 @@ class DecodeNmsOp(Op):
             m = self.mask
             ctx.call("ssdseg_seg_suppress", m.buf, m.m, m.c, self.probs.buf, b * a, self.probs_s)
 
-    def run_nms(self, boxes_iou_threshold=None, labels_probability_threshold=None, out: Optional[H.DeviceBuffer] = None):
-        """the NMS call alone on what decode() left, with the layer's thresholds or the given ones (a threshold grid re-runs only
-        this: NB03#cell21), into the op's output or `out` [b][max_total][6]"""
+    def run_nms(self, boxes_iou_threshold=None, labels_probability_threshold=None, soft_nms_sigma=None, out: Optional[H.DeviceBuffer] = None):
+        """the NMS call alone on what decode() left, with the layer's thresholds and Soft-NMS sigma or the given ones (a threshold
+        grid re-runs only this: NB03#cell21), into the op's output or `out` [b][max_total][6].  A sigma of 0 is the hard NMS,
+        ssdseg_combined_nms as ever; above 0 ssdseg_combined_nms_soft"""
         b, a, c = self.boxes.n, self.boxes.h * self.boxes.w, self.probs.c
         n = self.nms
         iou = n.boxes_iou_threshold if boxes_iou_threshold is None else boxes_iou_threshold
         prob = n.labels_probability_threshold if labels_probability_threshold is None else labels_probability_threshold
+        sigma = n.soft_nms_sigma if soft_nms_sigma is None else L.soft_nms_sigma_value(soft_nms_sigma)
         probs = self.probs_s if self.mask is not None else self.probs.buf
-        self.e.ctx.call("ssdseg_combined_nms", self.corners, probs, b, a, c, n.max_number_of_boxes_per_class, n.max_number_of_boxes_per_sample,
-                        float(iou), float(prob), self.out.buf if out is None else out, self.valid)
+        limits = (n.max_number_of_boxes_per_class, n.max_number_of_boxes_per_sample, float(iou), float(prob))
+        dst = self.out.buf if out is None else out
+        if sigma == 0:
+            self.e.ctx.call("ssdseg_combined_nms", self.corners, probs, b, a, c, *limits, dst, self.valid)
+        else:
+            self.e.ctx.call("ssdseg_combined_nms_soft", self.corners, probs, b, a, c, *limits, float(sigma), dst, self.valid)
 
     def fwd(self):
         self.decode()

@@ -146,6 +146,16 @@ def _nms_layer(model_inference):
     raise ValueError("evaluate_on_device needs a model from get_model_for_inference (no NMS output in this one)")
 
 
+def _grid_entry(entry) -> tuple:
+    """one nms_grid entry as a tuple of floats: (b_thr, p_thr), or (b_thr, p_thr, sigma) with a Soft-NMS sigma >= 0"""
+    from .layers import soft_nms_sigma_value
+    entry = tuple(entry)
+    if len(entry) not in (2, 3):
+        raise ValueError(f"evaluate_on_device: an nms_grid entry is (boxes_iou_threshold, labels_probability_threshold) or "
+                         f"(boxes_iou_threshold, labels_probability_threshold, soft_nms_sigma), got {entry!r}")
+    return (float(entry[0]), float(entry[1])) + tuple(soft_nms_sigma_value(s) for s in entry[2:])
+
+
 _NOT_PLAIN = {"rgb_draws": "the batch carries colour-augmentation draws",
               "crop_windows": "the batch carries crop windows; a test set is not augmented",
               "mosaic": "the batch carries a mosaic; a test set is not augmented",
@@ -183,19 +193,23 @@ def _labels_true(batch) -> List[np.ndarray]:
 
 
 def evaluate_on_device(model_inference, data, labels_codes: List[int], label_code_background: int, iou_thresholds: Sequence[float],
-                       nms_grid: Optional[Iterable[Tuple[float, float]]] = None, ignore_void: bool = False, confusion: bool = False) -> dict:
+                       nms_grid: Optional[Iterable[Tuple[float, ...]]] = None, ignore_void: bool = False, confusion: bool = False) -> dict:
     """The test-set evaluation of NB03#cell21-29 on a set the device holds.
 
     model_inference: from `get_model_for_inference` (suppress_background_boxes=False: with True the detections lose their batch
     axis, quirk Q7, and belong to no image; use_segmentation_suppression either way).  data: an iterable of
     `datacoder.CompactBatch`, a `ResidentDataset` (walked in slot order in its batch size, un-augmented, its generator untouched)
     or an iterable of `ResidentBatch`; no flips, no colour draws, no crop windows (ValueError).  nms_grid: (boxes_iou_threshold, labels_probability_threshold)
-    pairs, default the model's own.  Per batch the network and the decode (+ segmentation suppression) run once, the NMS once per
-    pair; segmentation suppression is batch-wide (quirk Q6), so the detections are those of `predict` on the same batches.
+    pairs or (boxes_iou_threshold, labels_probability_threshold, soft_nms_sigma) triples, default the model's own thresholds.  A
+    pair runs with the model's own soft_nms_sigma; a triple's sigma of 0 is the hard NMS, above 0 Gaussian Soft-NMS
+    (layers.soft_nms_reference; a negative or non-finite sigma or an entry of another length: ValueError).  Per batch the network
+    and the decode (+ segmentation suppression) run once, the NMS once per entry: a sigma sweep costs no network pass.
+    Segmentation suppression is batch-wide (quirk Q6), so the detections are those of `predict` on the same batches.
 
     -> {'iou': {label: soft Jaccard, mean over the samples (float64, sample order)},
-        'ap': {(b_thr, p_thr): {iou_threshold: {label: average precision}}},
-        'detections': {(b_thr, p_thr): (N, r, 6) rows (label, confidence, xmin, ymin, xmax, ymax)}}
+        'ap': {entry: {iou_threshold: {label: average precision}}},
+        'detections': {entry: (N, r, 6) rows (label, confidence, xmin, ymin, xmax, ymax)}}
+    with entry = the nms_grid entry as passed, as a tuple of floats: (b_thr, p_thr) or (b_thr, p_thr, sigma);
     without the background in 'iou' and 'ap', as jaccard_iou_semantic_segmentation / average_precision_object_detection, whose
     values these are (rows of label 0 are empty NMS rows and never count as predictions).
 
@@ -219,7 +233,7 @@ def evaluate_on_device(model_inference, data, labels_codes: List[int], label_cod
     if len(labels_codes) != n_cls:
         raise ValueError(f"{len(labels_codes)} label codes for a mask output of {n_cls} classes")
     pairs = [(float(nms.boxes_iou_threshold), float(nms.labels_probability_threshold))] if nms_grid is None \
-        else [(float(b), float(p)) for b, p in nms_grid]
+        else [_grid_entry(entry) for entry in nms_grid]
     thresholds = [float(t) for t in iou_thresholds]
     if not pairs or not thresholds:
         raise ValueError("evaluate_on_device: empty nms_grid or iou_thresholds")

@@ -70,10 +70,11 @@ class _SsdSegBuilderBase:
 
     def get_model_for_inference(self, model_trained: K.Model, max_number_of_boxes_per_class: int, max_number_of_boxes_per_sample: int,
                                 boxes_iou_threshold: float, labels_probability_threshold: float, suppress_background_boxes: bool,
-                                use_segmentation_suppression: bool) -> K.Model:
+                                use_segmentation_suppression: bool, soft_nms_sigma: float = 0.0) -> K.Model:
         """Trained graph + decode + (segmentation suppression) + combined NMS; outputs [mask, detections]
         (reference models.py:345-423 / :792-870).  The inference model shares the trained model's layers, so the
-        reference's layer-by-layer weight copy (:420-421) is the identity here."""
+        reference's layer-by-layer weight copy (:420-421) is the identity here.  soft_nms_sigma > 0 (not in the reference): the
+        NMS decays the scores of overlapping boxes instead of only deleting them (layers.NonMaximumSuppression)."""
         layer_input = model_trained.get_layer('backbone-input').output
         output_mask = model_trained.get_layer('output-mask').output
         boxes = model_trained.get_layer('output-boxes').output
@@ -90,7 +91,7 @@ class _SsdSegBuilderBase:
         nms = layers.NonMaximumSuppression(
             max_number_of_boxes_per_class=max_number_of_boxes_per_class, max_number_of_boxes_per_sample=max_number_of_boxes_per_sample,
             boxes_iou_threshold=boxes_iou_threshold, labels_probability_threshold=labels_probability_threshold,
-            suppress_background_boxes=suppress_background_boxes, name='output-object-detection')
+            suppress_background_boxes=suppress_background_boxes, soft_nms_sigma=soft_nms_sigma, name='output-object-detection')
         nms.trainable = False
         if use_segmentation_suppression:
             suppression = layers.SegmentationSuppression(name='segmentation-suppression')
