@@ -1,5 +1,5 @@
 """What the GPU edge suites (tests/test_gpu_tail_edges.py, tests/test_gpu_mask_edges.py, tests/test_gpu_dw_edges.py, tests/test_gpu_pw_edges.py,
-tests/test_gpu_conv3_edges.py) share: the error / bound ratio and its report,
+tests/test_gpu_conv3_edges.py, tests/test_gpu_stem_edges.py) share: the error / bound ratio and its report,
 the launches of a call read from the timing registry, bit comparisons, poison counts, views of guarded inputs, rejected calls."""
 import ctypes as C
 
